@@ -27,11 +27,18 @@ admission rule is applied once, after the merge: knowhere_amd/sharded.py::search
 127.0.0.1) and fails loudly when fewer than N GPUs are visible; `n_gpus` in the line is the size of the process group
 that really ran.  The timed loop rotates through `--query-batches` (3) distinct query batches, so nothing a step learns
 (the selectivity guard takes its decision from the previous batch's counters) is learnt from the batch it is applied to.
-The default run (C3, N = 1) also runs C2 through the same harness and reports it under "extra_configs".
+A plain run does only what the headline needs: build the index, warm up, time `--steps` steps, write the last timed step's
+results if `--dump-outputs DIR` is given, print the line.  Its "roofline" object comes from the stage timers of the same
+timed steps (no run of its own).  `--full` adds everything else the benchmark measures or checks: the recall gate
+(`recall_at_10`, `recall_gate_met`), the host-boundary timing ("host_boundary"), the CPU baseline ("cpu_baseline": the
+reference's own FAISS, AVX2 dynamic-dispatch build where it loads, timed on this box's host cores on a bounded sample of
+the same workload, checked bitwise against the GPU), the per-rank evidence of N > 1, and the further configurations
+(`--extra`; auto = C1, C1m, C2, C5s, C3u, C3l and, after the headline, C5 for the default C3 run on one GPU).
 
-Extra JSON objects: "roofline" (dominant kernel; for the ADC scan the binding unit is the LDS gather, HBM
-fractions are kept beside it) and "cpu_baseline" (the reference's own FAISS, AVX2 dynamic-dispatch build where it
-loads, timed on this box's host cores on a bounded sample of the same workload, checked bitwise against the GPU).
+`--dump-outputs DIR` writes what the last timed step returned: DIR/distances.npy (float32, [nq, k]) and DIR/ids.npy
+(float64, [nq, k]; -1 = no result).  Inputs are seeded, so two builds run with the same arguments can be compared output
+for output.  Should the pair exceed 64 MB, a fixed seeded sample of the query rows is written, their indices in
+DIR/rows.npy.
 """
 import argparse
 import json
@@ -109,21 +116,27 @@ def parse():
     ap.add_argument("--sigma", type=float, default=0.35)
     ap.add_argument("--ncenter", type=int, default=0, help="mixture components (0 = nb/160 rounded to a power of two)")
     ap.add_argument("--latent", type=int, default=0, help="intrinsic dimension of a component (0 = isotropic)")
-    ap.add_argument("--gt-queries", type=int, default=1000, help="queries used for the recall measurement")
+    ap.add_argument("--gt-queries", type=int, default=1000, help="queries used for the recall measurement (--full)")
     ap.add_argument("--cpu-queries", type=int, default=-1,
-                    help="queries of the CPU baseline sample (-1 = 32 per host thread, 0 = skip)")
+                    help="queries of the CPU baseline sample (--full; -1 = 32 per host thread, 0 = skip)")
     ap.add_argument("--query-batches", type=int, default=3, help="distinct query batches the timed loop rotates through")
     ap.add_argument("--extra", default="auto",
-                    help="further configurations run after the main one, one JSON line each: auto (= C1, C1m, C2, "
-                         "C5s, C3u, C3l for the default C3 run on one GPU), none, or a comma-separated list")
+                    help="further configurations run after the main one with --full, one JSON line each: auto (= C1, C1m, "
+                         "C2, C5s, C3u, C3l for the default C3 run on one GPU), none, or a comma-separated list")
     ap.add_argument("--dry-launch", action="store_true",
                     help="only bring the process group up and print its size (tests the --gpus N self-launch without a GPU)")
-    ap.add_argument("--host-steps", type=int, default=-1, help="steps of the host-boundary timing (-1 = --steps, 0 = skip)")
+    ap.add_argument("--host-steps", type=int, default=-1,
+                    help="steps of the host-boundary timing (--full; -1 = --steps, 0 = skip)")
     ap.add_argument("--backend", default=None, help="nccl (default for N>1) | gloo (single-GPU debugging)")
     ap.add_argument("--coarse-mode", default="auto", choices=["auto", "replicate", "shard"],
                     help="N > 1: coarse quantizer replicated on every rank (no collective) or sharded by queries (one "
                          "all-gather of the assignment); auto = shard")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: recall gate, host boundary, CPU baseline, N > 1 per-rank "
+                         "evidence, --extra configurations")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's distances and ids to DIR/*.npy")
     a = ap.parse_args()
     a.overridden = [key for key in SHAPE_KEYS if getattr(a, key, None) is not None] + (["data"] if a.data else [])
     apply_config(a, a.config, keep_overrides=True)
@@ -166,7 +179,9 @@ def self_launch(a):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     print("[bench] self-launch:", " ".join(cmd), file=sys.stderr, flush=True)
-    os.execvpe(cmd[0], cmd, env)
+    # (a child process, not exec: this process may already hold a HIP runtime from the device count above)
+    import subprocess
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def log(rank, *a):
@@ -213,6 +228,12 @@ def main():
             assert ndev >= world or os.environ.get("KNHIP_ALLOW_SHARED_GPU") == "1", \
                 f"{world} ranks on {ndev} GPU(s): set KNHIP_ALLOW_SHARED_GPU=1 for single-GPU debugging over gloo"
     out = run_config(a, rank, world, dev, dev_id, comm)
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(slim_line(out)), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     if rank == 0:
         # (a copy for the log as soon as it exists: should a later configuration take the process down, the headline
         # is still on stderr; stdout gets it LAST so that a tail of stdout always ends with it)
@@ -228,6 +249,7 @@ def main():
         import copy
         b = apply_config(copy.copy(a), name, keep_overrides=False)
         b.ncenter = 0
+        b.dump_outputs = None  # (the dump is the headline configuration's)
         if name in ("C3u", "C3l"):
             b.cpu_queries = 0  # (the same index kind and kernels as the main run: no second reference leg)
         torch.cuda.empty_cache()
@@ -251,6 +273,7 @@ def main():
         import copy
         b = apply_config(copy.copy(a), name, keep_overrides=False)
         b.ncenter = 0
+        b.dump_outputs = None  # (the dump is the headline configuration's)
         out_keep = slim_line(out) if rank == 0 else None
         torch.cuda.empty_cache()
         try:
@@ -335,6 +358,30 @@ def write_full(full):
         print(f"[bench] could not write gpurun_out/bench_full.json: {e!r}", file=sys.stderr)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, D, I):
+    """--dump-outputs: the (distances, ids) a caller of the timed step receives -> path/distances.npy (float32) and
+    path/ids.npy (float64: exact for every id below 2^53); above DUMP_LIMIT_BYTES a fixed, seeded sample of query rows
+    (their indices -> path/rows.npy)"""
+    D = D.float().cpu().numpy()
+    I = I.cpu().numpy().astype(np.float64)
+    nq = D.shape[0]
+    row_bytes = D[:1].nbytes + I[:1].nbytes
+    os.makedirs(path, exist_ok=True)
+    if nq * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(nq, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        D, I = D[rows], I[rows]
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    elif os.path.exists(os.path.join(path, "rows.npy")):
+        os.remove(os.path.join(path, "rows.npy"))  # (left by an earlier, larger dump)
+    np.save(os.path.join(path, "distances.npy"), D)
+    np.save(os.path.join(path, "ids.npy"), I)
+    print(f"[bench] outputs of the last timed step -> {path}: distances {D.shape} float32, ids {I.shape} float64",
+          file=sys.stderr, flush=True)
+
+
 def run_config(a, rank, world, dev, dev_id, comm):
     """build the configuration's index, gate recall, time the steps, collect roofline / host boundary / CPU baseline;
     returns the JSON object (rank 0) -- everything it allocated is released before it returns"""
@@ -402,7 +449,7 @@ def run_config(a, rank, world, dev, dev_id, comm):
     if getattr(built, "codes", None) is not None and built.codes.numel() > (16 << 30):
         # (C5: 76.8 GB of list-sorted codes: more than the host holds.  The reference leg runs on the SUB-INDEX the first
         # queries probe -- every list they visit, complete, the others empty: those queries get the whole index's answer)
-        if rank == 0 and world == 1 and a.cpu_queries != 0:
+        if rank == 0 and world == 1 and a.cpu_queries != 0 and a.full:
             from oracle import binding as ob  # checker / baseline only
             nsub = 24
             _, kk = g.coarse_search_device(xq[:nsub].contiguous(), a.nprobe)
@@ -483,14 +530,16 @@ def run_config(a, rank, world, dev, dev_id, comm):
             return g.search_refine(raw_bf, xq_host, a.k, kbase, a.nprobe)
         return g.search(xq_host, a.k, a.nprobe)
 
-    # ---------------------------------------------------------------- recall gate
+    # ---------------------------------------------------------------- recall gate (--full)
     D, I = step()
     torch.cuda.synchronize()
-    ngt = min(a.gt_queries, a.nq)
-    _, gt = kb.ground_truth(spec, xq[:ngt], a.k, metric=metric, device=str(dev))
-    hits = (I[:ngt].unsqueeze(2) == gt.unsqueeze(1)).any(dim=2).float().sum().item()
-    rec = hits / (ngt * a.k)
-    log(rank, f"recall@{a.k} = {rec:.4f} over {ngt} queries (refine_k={a.refine_k})")
+    rec = None
+    if a.full:
+        ngt = min(a.gt_queries, a.nq)
+        _, gt = kb.ground_truth(spec, xq[:ngt], a.k, metric=metric, device=str(dev))
+        hits = (I[:ngt].unsqueeze(2) == gt.unsqueeze(1)).any(dim=2).float().sum().item()
+        rec = hits / (ngt * a.k)
+        log(rank, f"recall@{a.k} = {rec:.4f} over {ngt} queries (refine_k={a.refine_k})")
     # a fingerprint of batch 0's (ids, distance bits): the same for every N when the same index is searched (the sharded
     # path returns the single GPU's answer bit for bit) -- lets the driver's N = 1, 2, 4, 8 lines be compared
     import zlib
@@ -510,8 +559,9 @@ def run_config(a, rank, world, dev, dev_id, comm):
     refine_ev["on"] = True
     barrier()
     t0 = time.perf_counter()
+    last = None
     for b in range(a.steps):
-        step(a.warmup + b)
+        last = step(a.warmup + b)
     barrier()
     dt = time.perf_counter() - t0
     refine_ev["on"] = False
@@ -521,8 +571,11 @@ def run_config(a, rank, world, dev, dev_id, comm):
     prof["bench_refine_ms"] = sum(e0.elapsed_time(e1) for e0, e1 in refine_ev["ev"])
     refine_ev["ev"] = []
     g.profile_enable(False)
+    if rank == 0 and a.dump_outputs and last is not None:
+        dump_outputs(a.dump_outputs, *last)
+    last = None
     multi = None
-    if world > 1:
+    if world > 1 and a.full:
         # per-rank evidence for the scaling curve, taken in a separate pass of the same steps (the events around the
         # collectives stay out of the timed region): stage times of every rank, time inside the collectives
         comm.timed = True
@@ -552,7 +605,7 @@ def run_config(a, rank, world, dev, dev_id, comm):
 
     host = None
     host_steps = a.steps if a.host_steps < 0 else a.host_steps
-    if world == 1 and host_steps > 0:
+    if world == 1 and host_steps > 0 and a.full:
         if refine:
             # the refine store knhip_search_refine reads: a BRUTE_FORCE index over the raw rows (a transient second copy here;
             # the node holds its rows in such an index from the start)
@@ -580,9 +633,9 @@ def run_config(a, rank, world, dev, dev_id, comm):
 
     roofline = make_roofline(a, kind, prof, world)
 
-    # ---------------------------------------------------------------- CPU baseline (rank 0, N == 1)
+    # ---------------------------------------------------------------- CPU baseline (rank 0, N == 1, --full)
     cpu = None
-    if rank == 0 and world == 1 and a.cpu_queries != 0:
+    if rank == 0 and world == 1 and a.cpu_queries != 0 and a.full:
         try:
             cpu = cpu_baseline(a, kind, metric, built, vectors, xq, D, I, g, log)
         except Exception as e:  # the baseline is a reported side number: never lose the bench line over it
@@ -599,7 +652,6 @@ def run_config(a, rank, world, dev, dev_id, comm):
             "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "value_form": "device-resident step (queries, index, raw rows in HBM); SURVEY 8(d)'s host-pointer form = host_boundary",
-            "recall_at_10": round(rec, 4), "recall_gate_met": bool(rec >= 0.95) if gate else None,
             "result_crc32": result_crc,
             "config": {"name": a.config,
                        "workload": f"{label}{' m=%d nbits=8' % a.m if kind == kidx.IVF_PQ else ''} {a.metric.upper()}, "
@@ -615,6 +667,9 @@ def run_config(a, rank, world, dev, dev_id, comm):
                        "build_s": round(build_s, 1)},
             "roofline": roofline,
         }
+        if rec is not None:
+            out["recall_at_10"] = round(rec, 4)
+            out["recall_gate_met"] = bool(rec >= 0.95) if gate else None
         if world > 1:
             out["scaling_note"] = ("strong scaling of one index over N ranks; the hardware curve is whatever the driver's "
                                    "SCALE run records -- none had been measured when this code was written")

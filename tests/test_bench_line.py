@@ -71,3 +71,24 @@ def test_slim_line_keeps_the_multi_gpu_block_small():
     m = json.loads(ln)["multi_gpu"]
     assert m["world"] == 8 and len(m["ranks"]) == 8
     assert len(json.dumps(m)) < 1024 + 8 * 40
+
+
+def test_dump_outputs_are_float_arrays_within_the_size_cap(tmp_path, monkeypatch):
+    """--dump-outputs: distances float32, ids float64 (exact), the same values; above the cap a fixed seeded row sample"""
+    import numpy as np
+    import torch
+    b = _bench()
+    D = torch.rand(50, 10)
+    I = torch.arange(500, dtype=torch.int64).reshape(50, 10) - 1
+    b.dump_outputs(str(tmp_path / "all"), D, I)
+    d, i = np.load(tmp_path / "all" / "distances.npy"), np.load(tmp_path / "all" / "ids.npy")
+    assert d.dtype == np.float32 and i.dtype == np.float64 and d.shape == i.shape == (50, 10)
+    assert d.tobytes() == D.numpy().tobytes() and (i == I.numpy()).all()
+    assert not (tmp_path / "all" / "rows.npy").exists()
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 20 * 10 * 12)
+    for run in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / run), D, I)
+    rows = np.load(tmp_path / "s1" / "rows.npy").astype(np.int64)
+    assert len(rows) == 20 and (np.diff(rows) > 0).all()
+    assert (np.load(tmp_path / "s1" / "ids.npy") == I.numpy()[rows]).all()
+    assert (np.load(tmp_path / "s2" / "rows.npy") == rows).all()  # the sample is the same from run to run

@@ -1,14 +1,14 @@
 #!/bin/bash
 # the driver's own command (N = 1), timed from outside; log + a one-line digest per configuration
-mkdir -p gpurun_out
+OUT="${OUT:-bench_logs}"; mkdir -p "$OUT"
 export TMPDIR=/tmp
 TAG="${1:-r05_bench_driver}"
 t0=$(date +%s)
-timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${TAG}.log 2>&1
+timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}.log 2>&1
 echo "rc=$? wall=$(( $(date +%s) - t0 ))s"
 python - <<PY
 import json
-for l in open("gpurun_out/${TAG}.log"):
+for l in open("$OUT/${TAG}.log"):
     if l.startswith("{"):
         d = json.loads(l)
         def show(n, x):
@@ -23,4 +23,4 @@ for l in open("gpurun_out/${TAG}.log"):
         for n, x in d.get("extra_configs", {}).items():
             show(n, x)
 PY
-grep -i "error\|traceback" gpurun_out/${TAG}.log | head -5
+grep -i "error\|traceback" $OUT/${TAG}.log | head -5

@@ -1,10 +1,10 @@
 #!/bin/bash
 # IVF-Flat / IVF-SQ8 prefilter paths: parity tests, then C2 and C5s with their stage tables
-mkdir -p gpurun_out
+OUT="${OUT:-bench_logs}"; mkdir -p "$OUT"
 export TMPDIR=/tmp
 TAG="${1:-r05_rowkinds}"
-timeout 900 python -m pytest tests/test_gpu_mscan.py tests/test_gpu_limits.py tests/test_gpu_parity.py tests/test_gpu_cosine.py tests/test_gpu_shards.py -q -m gpu -x > gpurun_out/${TAG}_tests.log 2>&1
-rc=$?; tail -4 gpurun_out/${TAG}_tests.log | cut -c1-400
+timeout 900 python -m pytest tests/test_gpu_mscan.py tests/test_gpu_limits.py tests/test_gpu_parity.py tests/test_gpu_cosine.py tests/test_gpu_shards.py -q -m gpu -x > $OUT/${TAG}_tests.log 2>&1
+rc=$?; tail -4 $OUT/${TAG}_tests.log | cut -c1-400
 show() {
 python - "$1" <<'PY'
 import json, sys
@@ -17,6 +17,6 @@ for l in open(sys.argv[1]):
 PY
 }
 if [ $rc -eq 0 ]; then
-  timeout 600 python bench.py --config C2 --steps 20 --warmup 5 --extra none --cpu-queries 128 --host-steps 0 > gpurun_out/${TAG}_c2.log 2>&1; show gpurun_out/${TAG}_c2.log
-  timeout 600 python bench.py --config C5s --steps 10 --warmup 3 --extra none --cpu-queries 64 --host-steps 0 > gpurun_out/${TAG}_c5s.log 2>&1; show gpurun_out/${TAG}_c5s.log
+  timeout 600 python bench.py --full --config C2 --steps 20 --warmup 5 --extra none --cpu-queries 128 --host-steps 0 > $OUT/${TAG}_c2.log 2>&1; show $OUT/${TAG}_c2.log
+  timeout 600 python bench.py --full --config C5s --steps 10 --warmup 3 --extra none --cpu-queries 64 --host-steps 0 > $OUT/${TAG}_c5s.log 2>&1; show $OUT/${TAG}_c5s.log
 fi

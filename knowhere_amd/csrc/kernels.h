@@ -274,6 +274,7 @@ struct MScanArgs {
     unsigned char* pq_spill;       // [pq_spill_wgs][pq_spill_cap] records of 80 bytes: where a workgroup parks passing lanes once its
     int32_t pq_spill_cap;          // LDS regions are full (a unit that is hot for many of its queries at once)
     int32_t pq_spill_wgs;          // workgroups the buffer serves (the launch takes no more)
+    const int2* pq_unit_tiles;     // [unit bound] {first tile, tiles}: the unit's chunk of its list (ms_units, cost cap); null: list-long
 };
 
 // ---- pq_filter.hip ----
@@ -374,10 +375,28 @@ hipError_t launch_ms_block_norms(const float4* rows, int64_t total_blk, int nchu
                                  hipStream_t s);
 hipError_t launch_ms_sq8_norms(const uint4* rows, int64_t total_blk, int nchunk16, int d, const float* trained,
                                float* out, float* out_max, hipStream_t s);
-// units from one virtual-list range of the work table (`*_v` = the table's arrays offset to that range)
+// units from one virtual-list range of the work table (`*_v` = the table's arrays offset to that range).
+// cost_cap > 0 (decode form): every (list, <= qt pairs) group is cut into chunks of whole 32-row tiles with
+// tiles x query tiles <= cost_cap (one tile at least), their tile ranges in unit_tiles (bound: ms_units_cost_bound)
 hipError_t launch_ms_units(const int32_t* list_count_v, const int64_t* list_pair_off_v, int64_t nlist, int qt,
                            int64_t* unit_off, int64_t* nunits, KnItem* units, const int64_t* list_len,
-                           int64_t code_size, double* unit_bytes, hipStream_t s);
+                           int64_t code_size, double* unit_bytes, hipStream_t s, int cost_cap = 0,
+                           int2* unit_tiles = nullptr);
+// units of a cut at cost_cap, at most (host side, no readback): npairs pairs in groups of <= qt over nlist lists of
+// ntotal rows, the longest max_len rows long
+inline int64_t ms_units_cost_bound(int64_t npairs, int qt, int64_t nlist, int64_t ntotal, int64_t max_len, int cost_cap) {
+    const int64_t groups = npairs / qt + std::min<int64_t>(nlist, npairs) + 1;
+    if (cost_cap <= 0) {
+        return groups;
+    }
+    const int64_t max_ntile = std::max<int64_t>((max_len + 31) / 32, 1);
+    // a group of ntq query tiles takes up to max(1, cap / ntq) tiles per chunk, and 1 / that <= 2 ntq / cap: its chunks
+    // are <= 1 + 2 ntile ntq / cap; the ntq of all groups sum to <= npairs / 32 + groups
+    const int64_t by_cost = groups + (2 * max_ntile * (npairs / 32 + groups) + cost_cap - 1) / cost_cap;
+    // and no more chunks than tiles (one for an empty list): full groups <= npairs / qt, one partial group per list
+    const int64_t by_tiles = npairs / qt * max_ntile + ntotal / 32 + 2 * nlist + 1;
+    return std::max<int64_t>(groups, std::min<int64_t>(by_cost, by_tiles));
+}
 hipError_t launch_mscan_flat(const MScanArgs& a, bool is_l2, int64_t units_bound, hipStream_t s);
 // ... its filter pass on the bf16 matrix pipe (mfma_scan_bf16.hip): queries per unit for this shape (0 = not served), LDS
 // bytes per workgroup, launch (a.dump must be null; units cut for mscan_flat_bf16_qt(a.nstep) queries)

@@ -965,6 +965,8 @@ int search_batch(const knhip_index* idx, Workspace* ws, const float* d_q, int64_
         }
         bool pq_i8 = false; // IVF-PQ: the integer form of the filter (chosen after the sample pass)
         bool pq_dec = false; // IVF-PQ: the decode form (pq_decode.hip)
+        int pqd_cost = 0;    // ... its units' cost cap (0: list-long units) and their number, at most
+        int64_t pqd_bound = 0;
         // which second form the guard weighs against the half tables: the decode form (default; its eps lies between the
         // half tables' and the int8 tables', its units hold 128 queries) or, when asked for, the int8 tables
         const bool pqd_ok = kind == KNHIP_IVF_PQ && pqd_supports(idx->desc.pq_m, d);
@@ -1218,6 +1220,17 @@ int search_batch(const knhip_index* idx, Workspace* ws, const float* d_q, int64_
                 }
                 if (pq_dec) {
                     qt = PD_QT;
+                    // units cut by cost (tiles x query tiles <= KNHIP_PQD_UNIT_COST): a long list probed by many queries
+                    // is several units, so no wave ends the launch alone on one, and a unit parks fewer records
+                    if (env.pqd_unit_cost > 0) {
+                        pqd_cost = env.pqd_unit_cost;
+                        pqd_bound = round_up(ms_units_cost_bound(npairs, PD_QT, nlist, idx->ntotal, idx->max_list_len,
+                                                                 pqd_cost), 8);
+                        HIP_TRY(ws->ms_units.reserve((size_t)pqd_bound * sizeof(KnItem)));
+                        HIP_TRY(ws->pqd_tiles.reserve((size_t)pqd_bound * sizeof(int2)));
+                        m.units = ws->ms_units.as<KnItem>(); // (the sample pass of IVF-PQ reads no units: nothing to keep)
+                        m.pq_unit_tiles = ws->pqd_tiles.as<int2>();
+                    }
                     m.pq_cb16 = idx->pqd_cb16.p;
                     m.pq_qh16 = ws->ms_qh16.p;
                     m.pq_qd = ws->ms_qd.as<float>();
@@ -1259,12 +1272,12 @@ int search_batch(const knhip_index* idx, Workspace* ws, const float* d_q, int64_
             HIP_TRY(launch_ms_units(w2.list_count + nlist, w2.list_pair_off + nlist, nlist, qt,
                                     ws->ms_unit_off.as<int64_t>(), ws->ms_nunits.as<int64_t>(),
                                     ws->ms_units.as<KnItem>(), idx->d_list_len.as<int64_t>(), idx->code_size,
-                                    idx->scan_bytes_dev.as<double>() + 2, s));
+                                    idx->scan_bytes_dev.as<double>() + 2, s, pqd_cost, ws->pqd_tiles.as<int2>()));
         }
         {
             // phase 2: every (query, list) pair on the matrix cores
             StageTimer t(idx, s, KNHIP_STAGE_SCAN);
-            HIP_TRY(launch_filter(m, units_bound));
+            HIP_TRY(launch_filter(m, std::max(units_bound, pqd_bound)));
         }
         {
             // phase 3: exact distances of the candidates -> final top-k.  phase 4: overflowed queries.  First a RETRY
@@ -1289,6 +1302,7 @@ int search_batch(const knhip_index* idx, Workspace* ws, const float* d_q, int64_
             r.units = ws->items.as<KnItem>();
             r.nunits_dev = wt.nitems;
             r.unit_loop = 1;
+            r.pq_unit_tiles = nullptr; // (the retry round's one-query units stay list-long)
             r.ghist = nullptr; // (the retried rows were counted once already: counting them again would fake k candidates)
             r.gmeta = nullptr;
             HIP_TRY(launch_filter(r, npairs));

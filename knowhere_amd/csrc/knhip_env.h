@@ -7,7 +7,7 @@
 //   * LAYOUT switches: read when an index lays out its lists / takes its rows / takes its coarse quantizer -- the index keeps
 //     what it read, a later change of the variable does not touch an existing index;
 //   * SEARCH switches: read by every search (tests flip them between two searches of one index: KNHIP_TIES,
-//     KNHIP_RANGE_NO_WAVES) -- six lookups per call.
+//     KNHIP_RANGE_NO_WAVES) -- eight lookups per call.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -42,7 +42,9 @@ struct EnvSearch {
     bool range_no_waves;   // KNHIP_RANGE_NO_WAVES: range search probes all lists in one pass
     bool ties_canonical;   // KNHIP_TIES=canonical|0: the canonical k without the boundary rule
     bool ties_trace;       // KNHIP_TIES_TRACE: one line per flagged batch on stderr
+    int pqd_unit_cost;     // KNHIP_PQD_UNIT_COST=n: decode-form units cut at n tiles x query tiles (0 = list-long units)
 };
+constexpr int KNHIP_PQD_UNIT_COST_DEFAULT = 512;
 
 inline bool env_is(const char* v, const char* what) { return v != nullptr && std::strcmp(v, what) == 0; }
 inline int env_digit(const char* v, int lo, int hi, int dflt) { return (v && v[0] >= '0' + lo && v[0] <= '0' + hi) ? v[0] - '0' : dflt; }
@@ -90,6 +92,8 @@ inline EnvSearch env_search() {
     const char* t = std::getenv("KNHIP_TIES");
     e.ties_canonical = t && (t[0] == 'c' || t[0] == 'C' || t[0] == '0');
     e.ties_trace = std::getenv("KNHIP_TIES_TRACE") != nullptr;
+    const char* uc = std::getenv("KNHIP_PQD_UNIT_COST");
+    e.pqd_unit_cost = (uc && *uc) ? std::max(0, std::atoi(uc)) : KNHIP_PQD_UNIT_COST_DEFAULT;
     return e;
 }
 

@@ -128,6 +128,7 @@ struct Workspace {
     DevBuf pq_recs, pq_ctr;                                          // pq_filter.hip: unit records, per-XCD counters
     DevBuf bf_kth;                                                   // BRUTE_FORCE on the matrix cores: the running k-th best per query over the chunks searched
     DevBuf ms_qh16, ms_qd, pq_spill;                                 // pq_decode.hip: the queries as halves, their error records, parked lanes beyond LDS
+    DevBuf pqd_tiles;                                                // pq_decode.hip: the units' tile ranges (cost-capped units)
     DevBuf rs_sort;                                                  // row selection of more than 16384 keys: sort scratch
     // host-boundary staging
     DevBuf h_queries, h_bitset, h_out_d, h_out_i, h_ref_d, h_ref_i;

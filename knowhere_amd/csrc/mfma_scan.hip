@@ -100,10 +100,31 @@ hipError_t launch_ms_block_norms(const float4* rows, int64_t total_blk, int nchu
 // cache line per thread and load)
 constexpr int MS_SCAN_THREADS = 1024;
 constexpr int MS_SCAN_PER = 4;
+// Cost cap (decode form): a group of npair pairs (ntq = ceil(npair / 32) query tiles) over a list of ntile 32-row tiles is
+// cut into ceil(ntile / max(1, cap / ntq)) chunks of whole tiles, sizes differing by one at most (only the list's last
+// chunk can end in a partial tile); an empty list keeps its one unit.  cap <= 0: one chunk.
+__device__ __forceinline__ int64_t ms_group_chunks(int64_t ntile, int npair, int cap) {
+    if (cap <= 0 || ntile <= 1) {
+        return 1;
+    }
+    const int ntq = (npair + 31) / 32;
+    const int64_t per = max(1, cap / ntq);
+    return (ntile + per - 1) / per;
+}
+// units of a list with c pairs: full groups of qt, then the rest
+__device__ __forceinline__ int64_t ms_list_units(int64_t c, int qt, int64_t len, int cap) {
+    const int64_t g = (c + qt - 1) / qt;
+    if (cap <= 0 || g == 0) {
+        return g;
+    }
+    const int64_t ntile = (len + 31) / 32;
+    return (g - 1) * ms_group_chunks(ntile, qt, cap) + ms_group_chunks(ntile, (int)(c - (g - 1) * qt), cap);
+}
 __global__ __launch_bounds__(MS_SCAN_THREADS) void ms_unit_scan_kernel(const int32_t* __restrict__ list_count_v,
                                                                        int64_t nlist, int qt,
                                                                        int64_t* __restrict__ unit_off,
-                                                                       int64_t* __restrict__ nunits) {
+                                                                       int64_t* __restrict__ nunits,
+                                                                       const int64_t* __restrict__ list_len, int cap) {
     constexpr int NW = MS_SCAN_THREADS / KN_WAVE;
     __shared__ long long s_w[NW];
     const int tid = threadIdx.x, lane = tid & (KN_WAVE - 1), wave = tid / KN_WAVE;
@@ -114,7 +135,7 @@ __global__ __launch_bounds__(MS_SCAN_THREADS) void ms_unit_scan_kernel(const int
 #pragma unroll
         for (int e = 0; e < MS_SCAN_PER; e++) {
             const int64_t l = l0 + e;
-            n[e] = l < nlist ? (list_count_v[l] + qt - 1) / qt : 0;
+            n[e] = l < nlist ? ms_list_units(list_count_v[l], qt, cap > 0 ? list_len[l] : 0, cap) : 0;
             tn += n[e];
         }
         long long in = tn; // inclusive scan over the wave's lanes
@@ -154,34 +175,47 @@ __global__ __launch_bounds__(MS_SCAN_THREADS) void ms_unit_scan_kernel(const int
 
 __global__ void ms_units_kernel(const int32_t* __restrict__ list_count_v, const int64_t* __restrict__ list_pair_off_v,
                                 const int64_t* __restrict__ unit_off, int64_t nlist, int qt, KnItem* __restrict__ units,
-                                const int64_t* __restrict__ list_len, int64_t code_size, double* unit_bytes) {
+                                const int64_t* __restrict__ list_len, int64_t code_size, double* unit_bytes, int cap,
+                                int2* __restrict__ unit_tiles) {
     const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (l >= nlist) {
         return;
     }
     const int64_t c = list_count_v[l];
     if (c > 0 && unit_bytes != nullptr) {
-        // bytes the prefilter streams: every unit reads its list once for up to qt queries
+        // bytes the prefilter streams: every (list, <= qt queries) group reads its list once (its chunks: once in total)
         atomicAdd(unit_bytes, (double)((c + qt - 1) / qt) * (double)list_len[l] * (double)code_size);
     }
     const int64_t p0 = list_pair_off_v[l];
+    const int64_t ntile = cap > 0 ? (list_len[l] + 31) / 32 : 0;
     int64_t u = unit_off[l];
-    for (int64_t i = 0; i < c; i += qt, u++) {
+    for (int64_t i = 0; i < c; i += qt) {
         KnItem x;
         x.list = (int32_t)l;
         x.npair = (int32_t)min((int64_t)qt, c - i);
         x.pair0 = p0 + i;
-        units[u] = x;
+        // (a list's chunks next to each other, in row order: the unit order the thresholds' freshness rests on)
+        const int64_t nch = ms_group_chunks(ntile, x.npair, cap);
+        for (int64_t j = 0; j < nch; j++, u++) {
+            units[u] = x;
+            if (cap > 0) {
+                const int64_t t0 = j * ntile / nch, t1 = (j + 1) * ntile / nch;
+                unit_tiles[u] = make_int2((int)t0, (int)(t1 - t0));
+            }
+        }
     }
 }
 
 hipError_t launch_ms_units(const int32_t* list_count_v, const int64_t* list_pair_off_v, int64_t nlist, int qt,
                            int64_t* unit_off, int64_t* nunits, KnItem* units, const int64_t* list_len,
-                           int64_t code_size, double* unit_bytes, hipStream_t s) {
+                           int64_t code_size, double* unit_bytes, hipStream_t s, int cost_cap, int2* unit_tiles) {
+    if (cost_cap > 0 && unit_tiles == nullptr) {
+        return hipErrorInvalidValue;
+    }
     hipLaunchKernelGGL(ms_unit_scan_kernel, dim3(1), dim3(MS_SCAN_THREADS), 0, s, list_count_v, nlist, qt, unit_off,
-                       nunits);
+                       nunits, list_len, cost_cap);
     hipLaunchKernelGGL(ms_units_kernel, dim3((unsigned)((nlist + 255) / 256)), dim3(256), 0, s, list_count_v,
-                       list_pair_off_v, unit_off, nlist, qt, units, list_len, code_size, unit_bytes);
+                       list_pair_off_v, unit_off, nlist, qt, units, list_len, code_size, unit_bytes, cost_cap, unit_tiles);
     return hipGetLastError();
 }
 

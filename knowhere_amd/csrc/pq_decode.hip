@@ -463,11 +463,12 @@ __device__ __forceinline__ void pd_wave_sync() {
 #endif
 }
 
-struct PdUnit {
-    int64_t len;      // rows of the list
-    int64_t row_off;  // first row of the list in the canonical arrays (codes, ids)
-    int64_t ps_off;   // first entry of the list in psum_s
+struct PdUnit {       // the unit's chunk of its list: tiles [t0, t0 + ntile) (the whole list without a cost cap)
+    int64_t len;      // rows of the chunk
+    int64_t row_off;  // first row of the chunk in the canonical arrays (codes, ids)
+    int64_t ps_off;   // first entry of the chunk in psum_s
     int ntile;        // ceil(len / 32)
+    uint32_t pos0;    // 32 t0: the chunk's first row in its list (candidates are list positions)
 };
 
 // One unit with NTQ query tiles: the wave walks the list's 32-row tiles 0, 1, ...  While tile t is multiplied (step
@@ -779,7 +780,9 @@ __device__ __forceinline__ int pqd_scan(const MScanArgs& a, unsigned char* smem,
 }
 
 // Persistent: one workgroup per CU keeps the codebook in LDS; after that its four waves never meet again -- every WAVE
-// pulls its own units (a list x <= 128 of the queries that probe it) in list order from its XCD's counter (the units of one
+// pulls its own units (a list x <= 128 of the queries that probe it; with a cost cap a chunk of the list's tiles,
+// a.pq_unit_tiles: no unit is a long list's whole tail of work, and its thresholds are read when the chunk starts) in list
+// order from its XCD's counter (the units of one
 // list run on one XCD, close in time: the second one finds the codes in that L2) and takes each from its first tile to the
 // appends of its passing rows alone, with its own pair arrays, parked records and counters in LDS.  (Until the middle of round 6
 // the four waves shared a unit, tiles dealt round-robin: per unit 10 k cycles went to the wave that had parked the most
@@ -956,10 +959,20 @@ __global__ __launch_bounds__(PD_THREADS, 1) void pqd_kernel(MScanArgs a) {
         const KnItem it = a.units[cur];
         const int ntq = (it.npair + 31) >> 5; // query tiles in use (uniform)
         PdUnit un;
-        un.len = a.list_len[it.list];
-        un.row_off = a.list_row_off[it.list];
-        un.ps_off = IS_L2 ? a.pq_sblk_off_r[it.list] * 16 : 0;
-        un.ntile = (int)((un.len + 31) >> 5);
+        {
+            const int64_t llen = a.list_len[it.list];
+            int t0 = 0, nt = (int)((llen + 31) >> 5);
+            if (a.pq_unit_tiles != nullptr) { // (a chunk of whole tiles: only the list's last chunk ends in a partial one)
+                const int2 tr = a.pq_unit_tiles[cur];
+                t0 = tr.x;
+                nt = tr.y;
+            }
+            un.pos0 = 32u * (uint32_t)t0;
+            un.len = min(llen - (int64_t)un.pos0, (int64_t)nt * 32);
+            un.row_off = a.list_row_off[it.list] + un.pos0;
+            un.ps_off = IS_L2 ? a.pq_sblk_off_r[it.list] * 16 + un.pos0 : 0;
+            un.ntile = nt;
+        }
         unsigned char* pa = pa_of(par);
         float* sT = reinterpret_cast<float*>(pa);
         float* sC = reinterpret_cast<float*>(pa + PD_QT * 4);
@@ -1022,10 +1035,11 @@ __global__ __launch_bounds__(PD_THREADS, 1) void pqd_kernel(MScanArgs a) {
                 const int at = atomicAdd(&ctl[1], 1);
                 if (at < PD_FLAT_CAP) {
                     const int rank = atomicAdd(&pcnt[pair], 1);
-                    flat[at] = make_uint4(pair, pos, xb, (uint32_t)rank);
+                    flat[at] = make_uint4(pair, un.pos0 + pos, xb, (uint32_t)rank);
                 } else { // (more passing rows than the list holds: appended on the spot)
                     const float xs = __uint_as_float(xb) * inv_sc, c = sC[pair];
-                    ms_emit<IS_L2>(a, sPq[pair], sPs[pair], un.row_off, (int64_t)pos, IS_L2 ? c - 2.0f * xs : c + xs);
+                    ms_emit<IS_L2>(a, sPq[pair], sPs[pair], un.row_off - un.pos0, (int64_t)(un.pos0 + pos),
+                                   IS_L2 ? c - 2.0f * xs : c + xs);
                 }
             }
         };

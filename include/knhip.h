@@ -27,6 +27,11 @@
  *                                        IndexShards (thirdparty/faiss/faiss/IndexShards.cpp:247-256)
  *   knhip_fvec_* / knhip_int8_*          the src/simd hook table (src/simd/hook.h:33-139),
  *                                        scalar semantics of src/simd/distances_ref.cc
+ *   knhip_iter_*                         IvfIndexNode::AnnIterator (src/index/ivf/ivf.cc:1502-1573) with
+ *                                        IVFIteratorWorkspace / IndexIterator (thirdparty/faiss/faiss/cppcontrib/knowhere/
+ *                                        IVFIteratorWorkspace.cpp:35-204, include/knowhere/index/index_node.h:1099-1247),
+ *                                        BruteForce::AnnIterator + PrecomputedDistanceIterator
+ *                                        (src/common/comp/brute_force.cc:1524-1760, index_node.h:1254-1390)
  *
  * Numeric contract ("exact" mode, the default): every distance is computed with the
  * reference's scalar operation order, one IEEE rounding per operation (no FMA contraction),
@@ -65,6 +70,7 @@ extern "C" {
  * 9: knhip_ties_rule_applies (one place decides whether a search follows the reference's boundary rule: single index, shard
  * group and the torch.distributed host agree); value 3 of the profile field pq_filter_form: the decode form of the IVF-PQ prefilter;
  * pq_nbits 1 .. 8 (host-side list codes in the reference's bit-string form).
+ * Additive since 9 (new functions only, no structure touched, the version stays 9): the AnnIterator, knhip_iter_*.
  * Callers compare knhip_abi_version() with the header they were built against. */
 #define KNHIP_ABI_VERSION 9
 
@@ -255,6 +261,44 @@ int knhip_range_search_ranked(const knhip_index* idx, const float* queries, int6
  * max_empty_result_buckets instead of nlist.  nlist when every list was scanned (max_empty = 0, or nlist <= 128). */
 int64_t knhip_index_last_range_ranks(const knhip_index* idx);
 void knhip_free(void* p);
+
+/* ---- AnnIterator: the results of a query one page at a time, in the reference's order ----------------------------------
+ * An iterator GROUP serves the nq queries of one AnnIterator call; its state lives in HBM.  Per query the sequence is the
+ * reference's, id for id and bit for bit:
+ *   IVF_FLAT / IVF_SQ8: the coarse quantizer ranks ALL nlist lists (best first); np = min(nprobe, nlist),
+ *     T = ntotal * np / nlist in unsigned integers (ntotal = the sum of the list sizes, the bitset ignored; T may be 0).
+ *     With A(r) = the bitset-passing rows of the query's ranks 0 .. r-1, the rows of rank r become eligible at result number
+ *     max(0, A(r) - T + 1); result number p is the smallest (sign * dist, id) -- value first, then id ascending, sign = -1 for
+ *     the inner product -- among the eligible rows not returned yet; the sequence ends when there is none.  So: T = 0 yields
+ *     nothing; with T > 0 every passing row of the index comes out (the walk covers all nlist lists, not nprobe of them); the
+ *     sequence is NOT globally sorted (a closer row of a list that is not eligible yet comes out later), as the reference's is
+ *     not.  Distances are the scanner's, those of knhip_range_search (row_scale of both cosine modes included).
+ *   BRUTE_FORCE: every passing row; L2: (dist asc, id asc), inner product / cosine: (dist desc, id DESC).  nprobe is ignored.
+ *   IVF_PQ: KNHIP_ERR_NOT_IMPLEMENTED, as the reference (is_ann_iterator_supported, src/index/ivf/ivf.cc:120-128).
+ * The sequence of a query does not depend on n, on how calls for different queries interleave, or on which of _next /
+ * _next_all served it.  Calls for DIFFERENT queries of one group may come from different host threads; two calls for the
+ * same query, or _next_all beside any other call, may not overlap.  The index must stay unmodified while a group lives.
+ * queries / bitset are HOST pointers; the group keeps device copies of both (the caller's buffers may go after create).
+ * Laziness: distances are computed for the eligible ranks only -- rows computed = A(frontier), what the reference computes.
+ * Memory of a group (bytes, HBM):
+ *   IVF kinds:   nq * 32 * min(T + Lp, ntotal)   two sorted pools per query, 16 B per entry (Lp = passing rows of the fullest list)
+ *                + 4 B per 64-row block of the lists + nq * d * 4 + bitset bytes
+ *                + per call in flight: 32 B per row that became eligible in its current round + 12 B per result of the page;
+ *                host: nq * (nlist + 1) * 16 B (coarse order and the prefix A).  No term in nq * ntotal unless nprobe = nlist.
+ *   BRUTE_FORCE: nq * ntotal * 4 (the key matrix) + 32 B per row of the slices selected so far, per query. */
+typedef struct knhip_iter knhip_iter;
+int knhip_iter_create(const knhip_index* idx, const float* queries, int64_t nq, int32_t nprobe, const uint8_t* bitset,
+                      int64_t bitset_nbits, knhip_iter** out);
+/* the next <= n results of query q; *got < n only at the end of the sequence */
+int knhip_iter_next(knhip_iter* it, int64_t q, int64_t n, int64_t* out_ids, float* out_dist, int64_t* got);
+/* the same for every query at once (one set of launches): out_ids / out_dist [nq][n], got [nq] */
+int knhip_iter_next_all(knhip_iter* it, int64_t n, int64_t* out_ids, float* out_dist, int64_t* got);
+int knhip_iter_has_next(knhip_iter* it, int64_t q); /* 1 / 0 / a negative knhip_status */
+/* what query q has cost so far: out[0] coarse ranks eligible for its next result (the reference's
+ * next_visit_coarse_list_idx), out[1] ranks whose distances were computed, out[2] rows whose distances were computed,
+ * out[3] results returned.  BRUTE_FORCE: 1, 1, the passing rows, results returned. */
+int knhip_iter_stats(const knhip_iter* it, int64_t q, int64_t out[4]);
+void knhip_iter_destroy(knhip_iter* it);
 
 /* ---- search ---- */
 /* Host boundary (what the IndexNode calls): queries [nq][dim] host fp32; bitset host bytes

@@ -63,6 +63,7 @@ SYMBOLS = [
     "knhip_fvec_L1_ny", "knhip_fvec_Linf_ny", "knhip_fvec_norms_L2sqr_ref", "knhip_fvec_L2sqr_ny_transposed",
     "knhip_fvec_L2sqr_ny_nearest", "knhip_fvec_L2sqr_ny_nearest_y_transposed", "knhip_fvec_madd_and_argmin",
     "knhip_fvec_batch_4", "knhip_typed_vec_ny", "knhip_typed_vec_batch_4", "knhip_ivec_ny",
+    "knhip_iter_create", "knhip_iter_next", "knhip_iter_next_all", "knhip_iter_has_next", "knhip_iter_stats", "knhip_iter_destroy",
 ]
 
 
@@ -101,6 +102,16 @@ def load():
                                             C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_int32))]
     L.knhip_free.argtypes = [vp]
     L.knhip_free.restype = None
+    # (a library given through KNHIP_LIB may be linked from a subset of the sources -- the CPU emulation of tests/hipemu --:
+    # the iterator's prototypes are bound where it exists; using it elsewhere fails on the missing symbol)
+    if hasattr(L, "knhip_iter_create"):
+        L.knhip_iter_create.argtypes = [vp, vp, i64, i32, vp, i64, C.POINTER(vp)]
+        L.knhip_iter_next.argtypes = [vp, i64, i64, vp, vp, C.POINTER(C.c_int64)]
+        L.knhip_iter_next_all.argtypes = [vp, i64, vp, vp, vp]
+        L.knhip_iter_has_next.argtypes = [vp, i64]
+        L.knhip_iter_stats.argtypes = [vp, i64, vp]
+        L.knhip_iter_destroy.argtypes = [vp]
+        L.knhip_iter_destroy.restype = None
     L.knhip_index_set_coarse.argtypes = [vp, vp]
     L.knhip_index_set_coarse_device.argtypes = [vp, vp]
     L.knhip_index_set_pq.argtypes = [vp, vp]

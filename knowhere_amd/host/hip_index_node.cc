@@ -19,6 +19,8 @@
 //           for k * refine_k candidates, re-ranked exactly on the device (knhip_search_refine).
 //   RangeSearch  IvfIndexNode::RangeSearch (ivf.cc:1231-1497) -> knhip_range_search; range_filter applied here
 //           (src/common/range_util.cc:27-48).  GetIndexMeta: not_implemented, as the cuVS node (gpu_cuvs.h:192-201).
+//   AnnIterator  IvfIndexNode::AnnIterator (ivf.cc:1502-1573) / BruteForce::AnnIterator -> one knhip_iter group per call,
+//           one iterator object per query serving Next() from a host page (FLAT, IVF_FLAT, IVF_SQ8; one device only).
 //   Devices cuvs_knowhere_index (src/common/cuvs/integration/cuvs_knowhere_index.cuh): every index instance owns a device --
 //           round-robin over the visible ones at Train (select_device_id, :414-426), the one with the most free
 //           memory at Deserialize (:678-690) -- or the `gpu_id` of the config.  `gpu_ids` with several ordinals deals
@@ -37,6 +39,7 @@
 #include <cmath>
 #include <cstdio>
 #include <atomic>
+#include <mutex>
 #include <numeric>
 #include <shared_mutex>
 #include <thread>
@@ -202,6 +205,103 @@ DealLists(const std::vector<int64_t>& sizes, int W) {
     }
     return owner;
 }
+
+// ---- AnnIterator: one knhip_iter group per call, one iterator object per query -----------------------------------------------------
+// The iterators of a call share the group (and with it the device copies of the queries and of the bitset: the caller's
+// buffers may go once AnnIterator has returned); each owns a host page it serves Next() from.  The first refill of ANY
+// iterator fetches the first page of the whole batch with one knhip_iter_next_all: creation stays cheap, the heavy work
+// happens in the first Next(), as the reference asks of its iterators (include/knowhere/index/index_node.h:1249-1253).
+// Like the reference's, an iterator is not thread safe; different iterators of a call may be advanced from different
+// threads (Milvus does, from a pool).  The node must outlive its iterators and stay unmodified, as in the reference
+// (the CPU iterator keeps a bare pointer to the faiss index, src/index/ivf/ivf.cc:1560).
+struct HipIterGroup {
+    knhip_iter* it = nullptr;
+    int64_t nq = 0;
+    std::mutex mu;  // the batch's first page
+    bool first_done = false;
+    int first_rc = KNHIP_OK;
+    std::string first_err;
+    std::vector<int64_t> first_ids;
+    std::vector<float> first_dis;
+    std::vector<int64_t> first_got;
+    ~HipIterGroup() {
+        if (it) knhip_iter_destroy(it);
+    }
+};
+
+class HipAnnIterator : public IndexNode::iterator {
+ public:
+    static constexpr int64_t kPage = 256;
+    HipAnnIterator(std::shared_ptr<HipIterGroup> g, int64_t q, const IdMap* id_map) : g_(std::move(g)), q_(q), id_map_(id_map) {
+    }
+    expected<std::pair<int64_t, float>>
+    Next() override {
+        using R = expected<std::pair<int64_t, float>>;
+        if (pos_ == ids_.size()) {
+            if (int rc = Refill()) return R::Err(ToStatus(rc), err_);
+        }
+        if (pos_ == ids_.size()) {
+            // (IndexIterator::next_impl, index_node.h:1144-1146)
+            return R::Err(Status::knowhere_inner_error, "No more elements");
+        }
+        int64_t id = ids_[pos_];
+        const float dis = dis_[pos_];
+        pos_++;
+        if (id_map_ != nullptr) id_map_->MapInToOut(&id, 1);
+        return std::make_pair(id, dis);
+    }
+    [[nodiscard]] expected<bool>
+    HasNext() override {
+        if (pos_ < ids_.size()) return true;
+        const int r = knhip_iter_has_next(g_->it, q_);
+        if (r < 0) return expected<bool>::Err(ToStatus(r), knhip_last_error());
+        return r == 1;
+    }
+
+ private:
+    int
+    Refill() {
+        ids_.clear();
+        dis_.clear();
+        pos_ = 0;
+        if (!started_) {
+            started_ = true;
+            std::lock_guard<std::mutex> lk(g_->mu);
+            if (!g_->first_done) {
+                g_->first_ids.resize((size_t)(g_->nq * kPage));
+                g_->first_dis.resize((size_t)(g_->nq * kPage));
+                g_->first_got.assign((size_t)g_->nq, 0);
+                g_->first_rc = knhip_iter_next_all(g_->it, kPage, g_->first_ids.data(), g_->first_dis.data(), g_->first_got.data());
+                if (g_->first_rc) g_->first_err = knhip_last_error();
+                g_->first_done = true;
+            }
+            if (g_->first_rc) {
+                err_ = g_->first_err;
+                return g_->first_rc;
+            }
+            const int64_t n = g_->first_got[(size_t)q_];
+            ids_.assign(g_->first_ids.begin() + q_ * kPage, g_->first_ids.begin() + q_ * kPage + n);
+            dis_.assign(g_->first_dis.begin() + q_ * kPage, g_->first_dis.begin() + q_ * kPage + n);
+            return KNHIP_OK;
+        }
+        ids_.resize((size_t)kPage);
+        dis_.resize((size_t)kPage);
+        int64_t got = 0;
+        const int rc = knhip_iter_next(g_->it, q_, kPage, ids_.data(), dis_.data(), &got);
+        if (rc) err_ = knhip_last_error();
+        ids_.resize((size_t)(rc ? 0 : got));
+        dis_.resize((size_t)(rc ? 0 : got));
+        return rc;
+    }
+    std::shared_ptr<HipIterGroup> g_;
+    int64_t q_;
+    const IdMap* id_map_;
+    std::vector<int64_t> ids_;
+    std::vector<float> dis_;
+    size_t pos_ = 0;
+    bool started_ = false;
+    std::string err_;
+};
 
 }  // namespace
 
@@ -631,6 +731,52 @@ class HipIndexNode : public IndexNode {
         auto res = GenResultDataSet(nq, out_ids.release(), out_dis.release(), out_lims.release());
         this->MapSearchResultIdsToOutIds(res);
         return res;
+    }
+
+    // IvfIndexNode::AnnIterator (ivf.cc:1502-1573) / the FLAT node's: one iterator per query row.  Statuses as the reference:
+    // empty_index, index_not_trained, not_implemented for IVF_PQ (is_ann_iterator_supported, ivf.cc:120-128).  COSINE: the
+    // query is copied and normalised (ivf.cc:1550-1557).  The bitset VIEW is copied to the device at creation (the
+    // reference keeps the view).  A node sharded with gpu_ids refuses.
+    expected<std::vector<IndexNode::IteratorPtr>>
+    AnnIterator(const DataSetPtr dataset, std::unique_ptr<Config> cfg, const BitsetView& bitset, bool /*use_knowhere_search_pool*/,
+                milvus::OpContext* op_context) const override {
+        using R = expected<std::vector<IndexNode::IteratorPtr>>;
+        if (!Built() || Count() == 0) return R::Err(Status::empty_index, "index not loaded");
+        if constexpr (Kind == KNHIP_IVF_PQ) {
+            return R::Err(Status::not_implemented, "index not supported: only FLAT, IVF_FLAT and IVF_SQ8 support Iterator");
+        }
+        if (sh_.size() > 1) {
+            return R::Err(Status::not_implemented, "AnnIterator is not supported on a node sharded with gpu_ids");
+        }
+        if (!dataset || !dataset->GetTensor() || !cfg) return R::Err(Status::invalid_args, "null dataset / config");
+        if (dataset->GetDim() != dim_) return R::Err(Status::invalid_args, "dim mismatch");
+        const auto& c = static_cast<const knowhere_config_type&>(*cfg);
+        int64_t nprobe = 1;
+        if constexpr (Kind != KNHIP_BRUTE_FORCE) nprobe = c.nprobe.value_or(default_nprobe_);
+        checkCancellation(op_context);
+        const int64_t nq = dataset->GetRows();
+        const float* q = (const float*)dataset->GetTensor();
+        std::vector<float> qn;
+        if (cosine_) {
+            qn.assign(q, q + nq * dim_);
+            NormalizeRows(qn.data(), nq, dim_);
+            q = qn.data();
+        }
+        std::vector<uint8_t> in_bitset;
+        const uint8_t* bits = nullptr;
+        int64_t nbits = 0;
+        MaterialiseBitset(bitset, &in_bitset, &bits, &nbits);
+        auto group = std::make_shared<HipIterGroup>();
+        group->nq = nq;
+        if (nq > 0) {
+            std::shared_lock<std::shared_mutex> lk(rw_);
+            const int rc = knhip_iter_create(sh_[0].idx.p, q, nq, (int32_t)nprobe, bits, nbits, &group->it);
+            if (rc) return R::Err(ToStatus(rc), knhip_last_error());
+        }
+        const IdMap* id_map = &this->GetIdMap();
+        std::vector<IndexNode::IteratorPtr> vec((size_t)nq);
+        for (int64_t i = 0; i < nq; i++) vec[(size_t)i] = std::make_shared<HipAnnIterator>(group, i, id_map);
+        return vec;
     }
 
     expected<DataSetPtr>

@@ -861,6 +861,23 @@ class IndexNode : public Object {
                 milvus::OpContext* op_context = nullptr) const {
         return expected<DataSetPtr>::Err(Status::not_implemented, "RangeSearch not implemented");
     }
+    // (include/knowhere/index/index_node.h:205-237: not thread safe; errors come back in the expected<>)
+    class iterator {
+     public:
+        virtual expected<std::pair<int64_t, float>>
+        Next() = 0;
+        [[nodiscard]] virtual expected<bool>
+        HasNext() = 0;
+        virtual ~iterator() {
+        }
+    };
+    using IteratorPtr = std::shared_ptr<iterator>;
+    virtual expected<std::vector<IteratorPtr>>
+    AnnIterator(const DataSetPtr dataset, std::unique_ptr<Config> cfg, const BitsetView& bitset,
+                bool use_knowhere_search_pool = true, milvus::OpContext* op_context = nullptr) const {
+        return expected<std::vector<std::shared_ptr<iterator>>>::Err(
+            Status::not_implemented, "annIterator not supported for current index type");
+    }
     virtual expected<DataSetPtr>
     GetVectorByIds(const DataSetPtr dataset, milvus::OpContext* op_context = nullptr) const = 0;
     virtual bool
@@ -941,6 +958,12 @@ class IndexNodeThreadPoolWrapper : public IndexNode {
                                      milvus::OpContext* op_context) const override {
         Slot s(this);
         return index_node_->RangeSearch(dataset, std::move(cfg), bitset, op_context);
+    }
+    // (creation only: the iterators advance outside the wrapper's slots, as in index_node_thread_pool_wrapper.h)
+    expected<std::vector<IteratorPtr>> AnnIterator(const DataSetPtr dataset, std::unique_ptr<Config> cfg,
+                                                   const BitsetView& bitset, bool use_knowhere_search_pool,
+                                                   milvus::OpContext* op_context) const override {
+        return index_node_->AnnIterator(dataset, std::move(cfg), bitset, use_knowhere_search_pool, op_context);
     }
     expected<DataSetPtr> GetVectorByIds(const DataSetPtr dataset, milvus::OpContext* op_context) const override {
         return index_node_->GetVectorByIds(dataset, op_context);
@@ -1078,6 +1101,22 @@ class Index {
             return node_->RangeSearch(dataset, std::move(cfg), node_->PrepareBitset(bitset), op_context);
         } catch (const std::exception& e) {
             return expected<DataSetPtr>::Err(Status::knowhere_inner_error, e.what());
+        }
+    }
+    // (src/index/index.cc: the ITERATOR parameter set, the bitset projected to the backend id domain)
+    expected<std::vector<IndexNode::IteratorPtr>>
+    AnnIterator(const DataSetPtr dataset, const Json& json, const BitsetView& bitset, bool use_knowhere_search_pool = true,
+                milvus::OpContext* op_context = nullptr) const noexcept {
+        using R = expected<std::vector<IndexNode::IteratorPtr>>;
+        try {
+            auto cfg = node_->CreateConfig();
+            std::string msg;
+            const Status s = LoadConfig(cfg.get(), json, PARAM_TYPE::ITERATOR, &msg);
+            if (s != Status::success) return R::Err(s, msg);
+            return node_->AnnIterator(dataset, std::move(cfg), node_->PrepareBitset(bitset), use_knowhere_search_pool,
+                                      op_context);
+        } catch (const std::exception& e) {
+            return R::Err(Status::knowhere_inner_error, e.what());
         }
     }
     expected<DataSetPtr>
@@ -1263,6 +1302,11 @@ struct BruteForce {
     static expected<DataSetPtr>
     RangeSearch(const DataSetPtr base_dataset, const DataSetPtr query_dataset, const Json& config, const BitsetView& bitset,
                 milvus::OpContext* op_context = nullptr);
+    // (include/knowhere/comp/brute_force.h:58-62)
+    template <typename DataType>
+    static expected<std::vector<IndexNode::IteratorPtr>>
+    AnnIterator(const DataSetPtr base_dataset, const DataSetPtr query_dataset, const Json& config, const BitsetView& bitset,
+                bool use_knowhere_search_pool = true, milvus::OpContext* op_context = nullptr) noexcept;
 };
 
 }  // namespace knowhere

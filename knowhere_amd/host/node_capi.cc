@@ -46,6 +46,10 @@ Json ParseConfig(const char* s) {
 struct Handle {
     Index<IndexNode> idx;
 };
+// the iterators of one Index::AnnIterator call
+struct IterHandle {
+    std::vector<IndexNode::IteratorPtr> its;
+};
 }  // namespace
 
 extern "C" {
@@ -125,6 +129,55 @@ int knhip_node_range_search(void* h, const float* q, int64_t nq, int64_t dim, co
     std::memcpy(*dist, r.value()->GetDistance(), sizeof(float) * n);
     return 0;
 }
+
+// Index::AnnIterator: one iterator per query row behind *out (release with knhip_node_iter_destroy).  The query and bitset
+// buffers may be released as soon as this returns.  Returns the Status value (0 = success).
+int knhip_node_iter_create(void* h, const float* q, int64_t nq, int64_t dim, const char* cfg, const uint8_t* bitset,
+                           int64_t nbits, void** out) {
+    *out = nullptr;
+    auto ds = GenDataSet(nq, dim, q);
+    auto r = static_cast<Handle*>(h)->idx.AnnIterator(ds, ParseConfig(cfg),
+                                                      bitset ? BitsetView(bitset, (size_t)nbits) : BitsetView());
+    if (!r.has_value()) {
+        g_err = r.what();
+        return (int)r.error();
+    }
+    *out = new IterHandle{r.value()};
+    return 0;
+}
+
+// iterator->Next() of query row i, up to n times: ids / dist receive the results, *got their number; the first failing
+// Next() ends the page and its Status is returned (past the end: the reference's knowhere_inner_error)
+int knhip_node_iter_next(void* it, int64_t i, int64_t n, int64_t* ids, float* dist, int64_t* got) {
+    auto* ih = static_cast<IterHandle*>(it);
+    *got = 0;
+    if (i < 0 || (size_t)i >= ih->its.size()) return (int)Status::invalid_args;
+    for (int64_t j = 0; j < n; j++) {
+        auto r = ih->its[(size_t)i]->Next();
+        if (!r.has_value()) {
+            g_err = r.what();
+            return (int)r.error();
+        }
+        ids[j] = r.value().first;
+        dist[j] = r.value().second;
+        *got = j + 1;
+    }
+    return 0;
+}
+
+// iterator->HasNext(): 1 / 0, or -Status
+int knhip_node_iter_has_next(void* it, int64_t i) {
+    auto* ih = static_cast<IterHandle*>(it);
+    if (i < 0 || (size_t)i >= ih->its.size()) return -(int)Status::invalid_args;
+    auto r = ih->its[(size_t)i]->HasNext();
+    if (!r.has_value()) {
+        g_err = r.what();
+        return -(int)r.error();
+    }
+    return r.value() ? 1 : 0;
+}
+
+void knhip_node_iter_destroy(void* it) { delete static_cast<IterHandle*>(it); }
 
 // the node's NormalizeVec restatement on n rows in place (norms may be null): test hook for the bitwise check against
 // knowhere::NormalizeVecs (src/common/utils.cc:60-93)

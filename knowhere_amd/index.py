@@ -280,6 +280,10 @@ class GpuIndex:
         self.L.knhip_free(pd)
         return lims, ids, dis
 
+    def iterator(self, xq, nprobe=1, bitset=None, nbits=0):
+        """knhip_iter_create -> GpuIterator: one iterator group for the rows of xq (the reference's AnnIterator order)"""
+        return GpuIterator(self, xq, nprobe, bitset, nbits)
+
     def range_search_ranked(self, xq, radius, bitset=None, nbits=0):
         """knhip_range_search_ranked -> (lims, ids, distances, counts[nq][nlist]): every list visited, hits per coarse rank"""
         xq = np.ascontiguousarray(xq, np.float32)
@@ -383,6 +387,67 @@ class GpuIndex:
                 "mscan_candidates": st.mscan_candidates, "mscan_stream_bytes": st.mscan_stream_bytes,
                 "mscan_recomputed": st.mscan_recomputed, "pq_filter_form": st.pq_filter_form,
                 "tie_queries": st.tie_queries, "tie_anomalies": st.tie_anomalies}
+
+
+class GpuIterator:
+    """Handle over a ``knhip_iter`` group.  The index must outlive it and stay unmodified; calls for different queries may
+    come from different threads."""
+
+    def __init__(self, index, xq, nprobe=1, bitset=None, nbits=0):
+        self.L = index.L
+        self.index = index  # (keeps the index alive)
+        xq = np.ascontiguousarray(xq, np.float32)
+        self.nq = xq.shape[0]
+        bs = None if bitset is None else np.ascontiguousarray(bitset, np.uint8)
+        nbits = _bitset_nbits(bs, nbits)
+        h = C.c_void_p()
+        self.h = None
+        check(self.L.knhip_iter_create(index.h, _np_ptr(xq), self.nq, int(nprobe), _np_ptr(bs), nbits, C.byref(h)))
+        self.h = h
+
+    def next(self, q, n):
+        """-> (ids, distances) of the next <= n results of query q; shorter only at the end of the sequence"""
+        ids = np.empty(max(n, 1), np.int64)
+        dis = np.empty(max(n, 1), np.float32)
+        got = C.c_int64(0)
+        check(self.L.knhip_iter_next(self.h, int(q), int(n), _np_ptr(ids), _np_ptr(dis), C.byref(got)))
+        return ids[:got.value].copy(), dis[:got.value].copy()
+
+    def next_all(self, n):
+        """-> (ids [nq][n], distances [nq][n], got [nq]): the next <= n results of every query, one set of launches"""
+        ids = np.full((self.nq, max(n, 1)), -1, np.int64)
+        dis = np.zeros((self.nq, max(n, 1)), np.float32)
+        got = np.zeros(self.nq, np.int64)
+        check(self.L.knhip_iter_next_all(self.h, int(n), _np_ptr(ids), _np_ptr(dis), _np_ptr(got)))
+        return ids[:, :n], dis[:, :n], got
+
+    def has_next(self, q):
+        r = self.L.knhip_iter_has_next(self.h, int(q))
+        check(min(r, 0))
+        return r == 1
+
+    def stats(self, q):
+        """-> (ranks eligible, ranks computed, rows computed, results returned) of query q"""
+        out = np.zeros(4, np.int64)
+        check(self.L.knhip_iter_stats(self.h, int(q), _np_ptr(out)))
+        return tuple(int(v) for v in out)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.knhip_iter_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def kmeans_device(metric, x_t, k, niter=None, max_points=None, seed=None, spherical=False):

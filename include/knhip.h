@@ -134,6 +134,20 @@ int knhip_index_set_coarse(knhip_index* idx, const float* centroids);
 int knhip_index_set_pq(knhip_index* idx, const float* codebooks);
 /* SQ8 trained params: vmin[dim], vdiff[dim] (ScalarQuantizer::trained) */
 int knhip_index_set_sq(knhip_index* idx, const float* vmin, const float* vdiff);
+/* IVF_SQ8: the code width of the list codes, the reference's sq_type (IvfSqConfig::sq_type -> QT_8bit / QT_6bit / QT_4bit of
+ * a residual IndexIVFScalarQuantizer): bits = 8 (default), 6 or 4.  Additive to ABI 9.  Settable only on a KNHIP_IVF_SQ8
+ * index that holds no rows yet; KNHIP_ERR_INVALID_ARGS for another value, another kind, or an index with rows.  The trained
+ * ranges (knhip_index_set_sq / knhip_index_train*) do not depend on the width.  List codes, on the HOST side
+ * (knhip_index_add_lists / knhip_index_get_lists) and the DEVICE side (knhip_index_encode_device,
+ * knhip_index_set_lists_device) alike, are the reference's code bytes:
+ *   8 bits: dim bytes per row, byte i = dimension i                                        (Codec8bit)
+ *   6 bits: (dim * 6 + 7) / 8 bytes, dimension i = bits 6i .. 6i+5 of a little-endian bit string (Codec6bit)
+ *   4 bits: (dim + 1) / 2 bytes, dimension i = the low (even i) or high nibble of byte i / 2     (Codec4bit)
+ * and stay packed in HBM (64-row blocks of 16-byte chunks of that byte string), so knhip_index_device_bytes shrinks with
+ * the width.  Search, RangeSearch and the AnnIterator read them with the exact kernel; the matrix-core prefilter serves 8-bit
+ * codes only.  knhip_index_get_sq_type returns the width, or 0 for an index of another kind. */
+int knhip_index_set_sq_type(knhip_index* idx, int32_t bits);
+int32_t knhip_index_get_sq_type(const knhip_index* idx);
 /* COSINE with stored norms, as the CPU nodes keep it for FLAT and IVF_FLAT: raw rows + one float per row, applied to the
  * finished inner product of every scanned row (Search and RangeSearch):
  *   mode 1: dis = <q, y> / scale      IVFFlatScanner with code norms (cppcontrib/knowhere/IndexIVFFlat.cpp:199-210),

@@ -41,7 +41,7 @@ class StageTimes(C.Structure):
 # every symbol include/knhip.h declares (tests check the .so exports all of them)
 SYMBOLS = [
     "knhip_abi_version", "knhip_device_count", "knhip_last_error", "knhip_index_create",
-    "knhip_index_destroy", "knhip_index_set_coarse", "knhip_index_set_pq", "knhip_index_set_sq", "knhip_index_set_row_scale", "knhip_index_add_assigned_by", "knhip_index_get_desc",
+    "knhip_index_destroy", "knhip_index_set_coarse", "knhip_index_set_pq", "knhip_index_set_sq", "knhip_index_set_sq_type", "knhip_index_get_sq_type", "knhip_index_set_row_scale", "knhip_index_add_assigned_by", "knhip_index_get_desc",
     "knhip_index_add_lists", "knhip_index_add_vectors", "knhip_index_set_coarse_device",
     "knhip_index_set_lists_device", "knhip_index_add_vectors_device", "knhip_index_count",
     "knhip_index_device_bytes", "knhip_index_uses_precomputed_table", "knhip_index_last_range_ranks", "knhip_search",
@@ -65,6 +65,14 @@ SYMBOLS = [
     "knhip_fvec_batch_4", "knhip_typed_vec_ny", "knhip_typed_vec_batch_4", "knhip_ivec_ny",
     "knhip_iter_create", "knhip_iter_next", "knhip_iter_next_all", "knhip_iter_has_next", "knhip_iter_stats", "knhip_iter_destroy",
 ]
+
+
+def sq_code_size(dim, sq_type=8):
+    """bytes per row of an IVF-SQ list code as the reference stores it: sq_type 8 -> dim, 6 -> (6 dim + 7) / 8 (four codes in
+    three bytes), 4 -> (dim + 1) / 2 (two codes per byte, the even dimension in the low nibble)"""
+    if sq_type not in (8, 6, 4):
+        raise ValueError(f"sq_type must be 8, 6 or 4 (bits per code), not {sq_type!r}")
+    return (dim * sq_type + 7) // 8
 
 
 class TrainParams(C.Structure):
@@ -116,6 +124,9 @@ def load():
     L.knhip_index_set_coarse_device.argtypes = [vp, vp]
     L.knhip_index_set_pq.argtypes = [vp, vp]
     L.knhip_index_set_sq.argtypes = [vp, vp, vp]
+    L.knhip_index_set_sq_type.argtypes = [vp, i32]
+    L.knhip_index_get_sq_type.argtypes = [vp]
+    L.knhip_index_get_sq_type.restype = i32
     L.knhip_index_set_row_scale.argtypes = [vp, vp, i32]
     L.knhip_index_add_assigned_by.argtypes = [vp, i64, vp, vp, vp]
     L.knhip_index_add_lists.argtypes = [vp, vp, vp, vp]

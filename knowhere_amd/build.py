@@ -129,6 +129,7 @@ class BuiltIndex:
 
     def __init__(self):
         self.kind = self.metric = self.d = self.nlist = self.M = None
+        self.sq_type = 8                   # IVF_SQ8: code width in bits (8, 6, 4); codes are then the packed bytes
         self.centroids = self.codebooks = self.sq_trained = None
         self.codes = self.ids = None       # list-sorted, ids ascending inside a list
         self.list_offsets = None           # numpy int64 [nlist+1]
@@ -142,7 +143,8 @@ class BuiltIndex:
         g = self.gpu if owned_lists is None else None
         self.gpu = None  # handed out at most once (the caller owns and closes it); further calls build a new handle
         if g is None or g.h is None or g.device != device:
-            g = GpuIndex(self.kind, self.metric, self.d, nlist=self.nlist, pq_m=self.M or 0, device=device)
+            g = GpuIndex(self.kind, self.metric, self.d, nlist=self.nlist, pq_m=self.M or 0, device=device,
+                         sq_type=self.sq_type)
             g.set_coarse_device(self.centroids)
             if self.kind == IVF_PQ:
                 g.set_pq(self.codebooks.cpu().numpy())
@@ -194,7 +196,7 @@ class BuiltIndex:
 
 def build_ivf(spec, kind, metric, nlist, M=32, device="cuda:0", train_per_centroid=256, niter=None,
               pq_train=1 << 20, centroids=None, codebooks=None, sq_trained=None, row_range=None, verbose=False,
-              keep_vectors=False, train_only=False, owned_lists=None):
+              keep_vectors=False, train_only=False, owned_lists=None, sq_type=8):
     """Train (unless centroids/codebooks are given, e.g. broadcast from rank 0) and encode
     rows [row_range) of the synthetic data set.  Returns a BuiltIndex on `device`.
     Clustering defaults are the reference's: 25 iterations, at most 256 training points per centroid
@@ -207,7 +209,8 @@ def build_ivf(spec, kind, metric, nlist, M=32, device="cuda:0", train_per_centro
     d = spec.d
     out = BuiltIndex()
     out.kind, out.metric, out.d, out.nlist, out.M = kind, metric, d, nlist, (M if kind == IVF_PQ else 0)
-    g = GpuIndex(kind, metric, d, nlist=nlist, pq_m=out.M, device=dev.index or 0)
+    g = GpuIndex(kind, metric, d, nlist=nlist, pq_m=out.M, device=dev.index or 0, sq_type=sq_type)
+    out.sq_type = sq_type
     out.gpu = g
     t0 = time.time()
     lo, hi = row_range if row_range is not None else (0, spec.n)

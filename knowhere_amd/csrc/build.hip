@@ -284,6 +284,73 @@ hipError_t launch_sq8_encode(const float* resid, int64_t n, int d, const float* 
     return hipGetLastError();
 }
 
+// IVF-SQ list codes of 6 and 4 bits (QuantizerTemplate<Codec6bit / Codec4bit, NON_UNIFORM>::encode_vector, quantizers.h:
+// 124-137): xi as above, code = (int)(xi * 63.0) or (int)(xi * 15.0) -- a DOUBLE product in the reference (codecs.h:51, 71),
+// exact for a float in [0, 1], where the 8-bit codec multiplies in float.  The row is a little-endian bit string of BITS
+// bits per dimension: four 6-bit codes in three bytes, or two nibbles per byte with the even dimension low.  One thread
+// writes one whole unit (3 bytes / 1 byte), so no two threads touch a byte.
+template <int BITS>
+__global__ void sq_encode_kernel(const float* __restrict__ r, int64_t n, int d, const float* __restrict__ trained,
+                                 uint8_t* __restrict__ codes) {
+    constexpr int PER = BITS == 6 ? 4 : 2;   // dimensions per unit
+    constexpr int UB = BITS == 6 ? 3 : 1;    // bytes per unit
+    const int nunit = (d + PER - 1) / PER;
+    const int64_t cs = sq_code_size(d, BITS);
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * nunit) {
+        return;
+    }
+    const int64_t row = t / nunit;
+    const int u = (int)(t % nunit);
+    uint32_t w = 0u;
+#pragma unroll
+    for (int e = 0; e < PER; e++) {
+        const int j = PER * u + e;
+        if (j < d) {
+            const float vmin = trained[j], vdiff = trained[d + j];
+            float xi = 0.f;
+            if (vdiff != 0.f) {
+                xi = __fdiv_rn(fsub_x(r[row * d + j], vmin), vdiff);
+                if (xi < 0.f) {
+                    xi = 0.f;
+                }
+                if (xi > 1.0f) {
+                    xi = 1.0f;
+                }
+            }
+            w |= (uint32_t)(int)((double)xi * (double)((1 << BITS) - 1)) << (BITS * e);
+        }
+    }
+    uint8_t* o = codes + row * cs + (int64_t)u * UB;
+#pragma unroll
+    for (int j = 0; j < UB; j++) {
+        if ((int64_t)u * UB + j < cs) { // (a ragged last 6-bit unit owns fewer than three bytes)
+            o[j] = (uint8_t)(w >> (8 * j));
+        }
+    }
+}
+
+hipError_t launch_sq_encode(const float* resid, int64_t n, int d, int bits, const float* trained, uint8_t* codes,
+                            hipStream_t s) {
+    if (bits == 8) {
+        return launch_sq8_encode(resid, n, d, trained, codes, s);
+    }
+    if (bits != 6 && bits != 4) {
+        return hipErrorInvalidValue;
+    }
+    if (n <= 0) {
+        return hipSuccess;
+    }
+    const int per = bits == 6 ? 4 : 2;
+    const int64_t nthr = n * ((d + per - 1) / per);
+    if (bits == 6) {
+        hipLaunchKernelGGL(sq_encode_kernel<6>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, resid, n, d, trained, codes);
+    } else {
+        hipLaunchKernelGGL(sq_encode_kernel<4>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, resid, n, d, trained, codes);
+    }
+    return hipGetLastError();
+}
+
 // per column min / max over n rows: one workgroup per 64 columns, rows strided over waves (order independent)
 __global__ __launch_bounds__(256) void col_minmax_kernel(const float* __restrict__ x, int64_t n, int d, float* vmin,
                                                          float* vmax) {

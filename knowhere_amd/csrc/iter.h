@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "sq_codec.h"
 
 namespace knhip {
 
@@ -56,7 +57,8 @@ struct IterScanArgs {
     int64_t nrows; // dense row set
     const float* queries;
     const float* centroids;
-    const float* trained; // SQ8: vmin[d], vdiff[d]
+    const float* trained; // IVF-SQ: vmin[d], vdiff[d]
+    int32_t sq_bits;      // IVF-SQ: code width 8, 6 or 4 (0 = 8)
     const float* row_scale;
     int32_t cos_mode;
     int32_t id_desc;

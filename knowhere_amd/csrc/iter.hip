@@ -72,7 +72,7 @@ __global__ __launch_bounds__(IT_THREADS) void iter_accept_kernel(IterScanArgs a,
 }
 
 // ---- exact distances of the round's lists -> the segments ---------------------------------------------------------------
-template <bool IS_L2, int KIND>
+template <bool IS_L2, int KIND, int BITS = 8>
 __global__ __launch_bounds__(IT_THREADS) void iter_expand_kernel(IterScanArgs a, const IterWork* __restrict__ works,
                                                                  const IterPair* __restrict__ pairs, int64_t nchunk_max) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -119,13 +119,17 @@ __global__ __launch_bounds__(IT_THREADS) void iter_expand_kernel(IterScanArgs a,
             }
         }
     } else { // KNHIP_IVF_SQ8 (sq_scan.hip:72-153)
-        const int nchunk16 = (a.d + 15) / 16;
-        const int dpad = nchunk16 * 16;
+        using W = SqWidth<BITS>;
+        const int nchunk16 = sq_nchunk16(a.d, BITS);
+        const int ngroup = (nchunk16 + W::GROUP_CHUNKS - 1) / W::GROUP_CHUNKS;
+        const int dpad = ngroup * W::GROUP_DIMS;
         float* sy = reinterpret_cast<float*>(smem);
         float* svmin = sy + dpad;
         float* svdiff = svmin + dpad;
         float* tab = svdiff + dpad;
-        tab[threadIdx.x] = __fdiv_rn((float)threadIdx.x + 0.5f, 255.0f); // (IT_THREADS == 256 codes)
+        if (threadIdx.x < W::NCODE) { // (IT_THREADS == 256 >= the codes of any width)
+            tab[threadIdx.x] = sq_decode_xi<BITS>(threadIdx.x);
+        }
         for (int i = threadIdx.x; i < dpad; i += IT_THREADS) {
             float v = 0.f;
             if (i < a.d) {
@@ -142,13 +146,21 @@ __global__ __launch_bounds__(IT_THREADS) void iter_expand_kernel(IterScanArgs a,
         if (b * 64 < len) {
             const uint4* p = reinterpret_cast<const uint4*>(a.rows) + (blk0 + b) * (int64_t)nchunk16 * 64 + lane;
 #pragma unroll 2
-            for (int c = 0; c < nchunk16; c++) {
-                const uint4 w = p[(int64_t)c * 64];
-                const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+            for (int c = 0; c < ngroup; c++) {
+                uint32_t ww[4 * W::GROUP_CHUNKS];
 #pragma unroll
-                for (int e = 0; e < 16; e++) {
-                    const uint32_t code = (ww[e >> 2] >> (8 * (e & 3))) & 0xffu;
-                    const int i = c * 16 + e;
+                for (int g = 0; g < W::GROUP_CHUNKS; g++) {
+                    const int cc = c * W::GROUP_CHUNKS + g;
+                    const uint4 w = (W::GROUP_CHUNKS == 1 || cc < nchunk16) ? p[(int64_t)cc * 64] : make_uint4(0, 0, 0, 0);
+                    ww[4 * g + 0] = w.x;
+                    ww[4 * g + 1] = w.y;
+                    ww[4 * g + 2] = w.z;
+                    ww[4 * g + 3] = w.w;
+                }
+#pragma unroll
+                for (int e = 0; e < W::GROUP_DIMS; e++) {
+                    const uint32_t code = sq_group_code<BITS>(ww, e);
+                    const int i = c * W::GROUP_DIMS + e;
                     const float xi = tab[code];
                     const float x = fadd_x(svmin[i], fmul_x(xi, svdiff[i]));
                     const float y = sy[i];
@@ -455,8 +467,14 @@ hipError_t launch_iter_expand(const IterScanArgs& a, bool is_l2, const IterWork*
         auto kern = is_l2 ? iter_expand_kernel<true, KNHIP_IVF_FLAT> : iter_expand_kernel<false, KNHIP_IVF_FLAT>;
         hipLaunchKernelGGL(kern, grid, dim3(IT_THREADS), lds, s, a, works, pairs, nchunk);
     } else if (a.kind == KNHIP_IVF_SQ8) {
-        const size_t lds = ((size_t)((a.d + 15) / 16) * 16 * 3 + 256) * sizeof(float);
-        auto kern = is_l2 ? iter_expand_kernel<true, KNHIP_IVF_SQ8> : iter_expand_kernel<false, KNHIP_IVF_SQ8>;
+        const int bits = a.sq_bits == 0 ? 8 : a.sq_bits;
+        if (!sq_bits_valid(bits)) {
+            return hipErrorInvalidValue;
+        }
+        const size_t lds = ((size_t)sq_dpad(a.d, bits) * 3 + 256) * sizeof(float);
+        auto kern = bits == 8 ? (is_l2 ? iter_expand_kernel<true, KNHIP_IVF_SQ8, 8> : iter_expand_kernel<false, KNHIP_IVF_SQ8, 8>)
+                  : bits == 6 ? (is_l2 ? iter_expand_kernel<true, KNHIP_IVF_SQ8, 6> : iter_expand_kernel<false, KNHIP_IVF_SQ8, 6>)
+                              : (is_l2 ? iter_expand_kernel<true, KNHIP_IVF_SQ8, 4> : iter_expand_kernel<false, KNHIP_IVF_SQ8, 4>);
         hipLaunchKernelGGL(kern, grid, dim3(IT_THREADS), lds, s, a, works, pairs, nchunk);
     } else {
         return hipErrorInvalidValue;

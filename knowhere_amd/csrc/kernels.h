@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
+#include "sq_codec.h"
 
 namespace knhip {
 
@@ -178,7 +179,8 @@ struct SqScanArgs {
     const float* trained;        // vmin[d], vdiff[d]
     const float* centroids;      // [nlist][d]  (L2: query residual)
     int32_t d;
-    int32_t nchunk16;            // ceil(d/16)
+    int32_t nchunk16;            // 16-byte chunks per stored row: ceil(code_size / 16) (sq_codec.h)
+    int32_t bits;                // code width: 8, 6 or 4 (0 = 8)
     const float* queries;        // [nq][d]
     const float* coarse_dis;     // [nq][nprobe] (IP: accu0)
     const KnItem* items;
@@ -209,8 +211,10 @@ struct MScanArgs {
     const float* trained;        // SQ8: vmin[d], vdiff[d]
     const float* centroids;      // SQ8 L2: query residual
     int32_t d;
-    int32_t nchunk;              // fp32: ceil(d / 4) float4 chunks; SQ8: ceil(d / 16) code chunks
-    int32_t nstep;               // fp32: ceil(nchunk / 4) steps of 16 dims; SQ8: ceil(nchunk / 2) steps of 32 dims
+    int32_t nchunk;              // fp32: ceil(d / 4) float4 chunks; IVF-SQ: 16-byte chunks of a row's packed codes
+    int32_t nstep;               // fp32: ceil(nchunk / 4) steps of 16 dims; IVF-SQ: steps of 32 dims (8 bits: two chunks) or
+                                 // 64 dims (4 bits: two chunks, 6 bits: three) -- sq_codec.h SqStep
+    int32_t sq_bits;             // IVF-SQ: code width 8, 6 or 4 (0 = 8)
     const float* queries;
     const float* qnorm;          // [nq] ||q||^2 (fp32 rows)
     const float* coarse_dis;     // [nq][nslot] (SQ8 IP: accu0)
@@ -368,13 +372,13 @@ hipError_t launch_pq_cb_transpose(const float* cb, int M, int dsub, float4* cb_t
 // ---- mfma_scan.hip ----
 int mscan_queries_per_unit(int kind, bool sample);
 size_t mscan_flat_smem(int nstep);
-size_t mscan_sq8_smem(int nstep);
+size_t mscan_sq8_smem(int nstep, int bits = 8);
 int mscan_finish_pmax(int cap, int k);
 int mscan_sample_rows();
 hipError_t launch_ms_block_norms(const float4* rows, int64_t total_blk, int nchunk, float* out, float* out_max,
                                  hipStream_t s);
 hipError_t launch_ms_sq8_norms(const uint4* rows, int64_t total_blk, int nchunk16, int d, const float* trained,
-                               float* out, float* out_max, hipStream_t s);
+                               float* out, float* out_max, hipStream_t s, int bits = 8);
 // units from one virtual-list range of the work table (`*_v` = the table's arrays offset to that range).
 // cost_cap > 0 (decode form): every (list, <= qt pairs) group is cut into chunks of whole 32-row tiles with
 // tiles x query tiles <= cost_cap (one tile at least), their tile ranges in unit_tiles (bound: ms_units_cost_bound)
@@ -407,7 +411,7 @@ hipError_t launch_mscan_sq8(const MScanArgs& a, bool is_l2, int64_t units_bound,
 hipError_t launch_ms_sample_plan(const int64_t* keys, int64_t nq, int nprobe, int64_t nlist, const int64_t* list_len,
                                  int smin, int cap, int32_t* sample_off, int32_t* n_row, hipStream_t s);
 hipError_t launch_ms_sq8_query_prep(const float* queries, int64_t nq, int d, int ldq, const float* trained, void* qh,
-                                    void* ql, float* qs, hipStream_t s);
+                                    void* ql, float* qs, hipStream_t s, int bits = 8);
 hipError_t launch_ms_tau(const float* sel_d, int64_t nq, int k, bool is_l2, float* gthr, uint2* gmeta, hipStream_t s);
 hipError_t launch_mscan_finish(const MScanArgs& a, int kind, bool is_l2, const int64_t* keys, const float* coarse_dis,
                                int nprobe, int k, float* out_d, int64_t* out_i, unsigned long long* counters, int pass,
@@ -420,7 +424,7 @@ hipError_t launch_ms_flag_pairs(const int32_t* overflow, int want, const int64_t
 hipError_t launch_sq_scan(const SqScanArgs& a, bool is_l2, int64_t grid, hipStream_t s, int qg_override = 0);
 hipError_t launch_sq_interleave(const uint8_t* codes, const int64_t* list_row_off,
                                 const int64_t* list_len, const int64_t* list_blk_off, int64_t nlist,
-                                int d, uint4* out, hipStream_t s);
+                                int64_t code_size, uint4* out, hipStream_t s);
 
 // ---- worktable.hip: (query, probe) pairs -> per-list work items ----
 struct WorkTable {
@@ -626,6 +630,9 @@ hipError_t launch_nearest_small(const float* x, int64_t n, int64_t ld, int off, 
                                 int32_t* out_idx, hipStream_t s);
 hipError_t launch_pq_encode(const float* resid, int64_t n, int d, int M, const float* cb, uint8_t* codes, hipStream_t s);
 hipError_t launch_sq8_encode(const float* resid, int64_t n, int d, const float* trained, uint8_t* codes, hipStream_t s);
+// IVF-SQ list codes of any width (bits = 8, 6, 4): codes [n][sq_code_size(d, bits)], the reference's bytes
+hipError_t launch_sq_encode(const float* resid, int64_t n, int d, int bits, const float* trained, uint8_t* codes,
+                            hipStream_t s);
 hipError_t launch_col_minmax(const float* x, int64_t n, int d, float* vmin, float* vmax, hipStream_t s);
 size_t group_rows_tmp_bytes(int64_t n, int64_t k);
 hipError_t group_rows_by_key(const int64_t* keys64, const int32_t* keys32, int64_t n, int64_t k, int32_t* sorted_rows,

@@ -336,11 +336,11 @@ int build_list_layout(knhip_index* idx, const std::vector<int64_t>& list_off, co
                                        idx->d_list_blk_off2.as<int64_t>(), nlist, idx->rows2.as<uint4>(), nullptr));
         }
     } else if (kind == KNHIP_IVF_SQ8) {
-        const int nchunk16 = (idx->d + 15) / 16;
+        const int nchunk16 = sq_nchunk16(idx->d, idx->sq_bits);
         HIP_TRY(idx->rows.alloc((size_t)total_blk * nchunk16 * 64 * sizeof(uint4)));
         HIP_TRY(launch_sq_interleave(d_codes, idx->d_list_row_off.as<int64_t>(),
                                      idx->d_list_len.as<int64_t>(), idx->d_list_blk_off.as<int64_t>(),
-                                     nlist, idx->d, idx->rows.as<uint4>(), nullptr));
+                                     nlist, idx->code_size, idx->rows.as<uint4>(), nullptr));
     } else {
         return fail(KNHIP_ERR_INVALID_ARGS, "lists on a brute-force index");
     }
@@ -382,8 +382,8 @@ int ensure_mscan_norms(const knhip_index* idx) {
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(&idx->xnorm_max, xmax, sizeof(float), hipMemcpyDeviceToHost));
     } else {
-        HIP_TRY(launch_ms_sq8_norms(idx->rows.as<uint4>(), total_blk, (idx->d + 15) / 16, idx->d,
-                                    idx->sq_trained.as<float>(), xn, xmax, nullptr));
+        HIP_TRY(launch_ms_sq8_norms(idx->rows.as<uint4>(), total_blk, sq_nchunk16(idx->d, idx->sq_bits), idx->d,
+                                    idx->sq_trained.as<float>(), xn, xmax, nullptr, idx->sq_bits));
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(&idx->xnorm_max, xmax, sizeof(float), hipMemcpyDeviceToHost));
     }
@@ -782,9 +782,10 @@ int search_batch(const knhip_index* idx, Workspace* ws, const float* d_q, int64_
             ms_nstep = (ms_nchunk + 3) / 4;
             lds = mscan_flat_smem(ms_nstep);
         } else {
-            ms_nchunk = (d + 15) / 16;
-            ms_nstep = (ms_nchunk + 1) / 2;
-            lds = mscan_sq8_smem(ms_nstep);
+            const int step_chunks = idx->sq_bits == 6 ? 3 : 2; // (sq_codec.h SqStep: 32 dims for 8 bits, 64 for 6 and 4)
+            ms_nchunk = sq_nchunk16(d, idx->sq_bits);
+            ms_nstep = (ms_nchunk + step_chunks - 1) / step_chunks;
+            lds = mscan_sq8_smem(ms_nstep, idx->sq_bits);
         }
         // candidate capacity per query: the finish kernel sorts them in LDS (a power of two entries)
         // candidate capacity per query (the finish kernel takes any number, in chunks): generous -- a query whose sample
@@ -922,6 +923,7 @@ int search_batch(const knhip_index* idx, Workspace* ws, const float* d_q, int64_
         m.d = d;
         m.nchunk = ms_nchunk;
         m.nstep = ms_nstep;
+        m.sq_bits = kind == KNHIP_IVF_SQ8 ? idx->sq_bits : 0;
         m.queries = d_q;
         m.qnorm = ws->qnorm.as<float>();
         m.coarse_dis = cdis_p;
@@ -1051,12 +1053,12 @@ int search_batch(const knhip_index* idx, Workspace* ws, const float* d_q, int64_
                 HIP_TRY(launch_row_norms(d_q, nq, d, ws->qnorm.as<float>(), s));
             } else if (!is_l2) {
                 // inner product: the query operand (scaled, split into two halves) is the same for every list
-                const int ldq = ms_nstep * 32;
+                const int ldq = ms_nstep * (idx->sq_bits == 8 ? 32 : 64);
                 HIP_TRY(ws->ms_qh.reserve((size_t)nq * ldq * 2));
                 HIP_TRY(ws->ms_ql.reserve((size_t)nq * ldq * 2));
                 HIP_TRY(ws->ms_qs.reserve((size_t)nq * 8 * sizeof(float)));
                 HIP_TRY(launch_ms_sq8_query_prep(d_q, nq, d, ldq, idx->sq_trained.as<float>(), ws->ms_qh.p, ws->ms_ql.p,
-                                                 ws->ms_qs.as<float>(), s));
+                                                 ws->ms_qs.as<float>(), s, idx->sq_bits));
                 m.qh = ws->ms_qh.p;
                 m.ql = ws->ms_ql.p;
                 m.qs = ws->ms_qs.as<float>();
@@ -1495,7 +1497,8 @@ int search_batch(const knhip_index* idx, Workspace* ws, const float* d_q, int64_
         a.trained = idx->sq_trained.as<float>();
         a.centroids = idx->centroids.as<float>();
         a.d = d;
-        a.nchunk16 = (d + 15) / 16;
+        a.nchunk16 = sq_nchunk16(d, idx->sq_bits);
+        a.bits = idx->sq_bits;
         a.queries = d_q;
         a.coarse_dis = cdis_p;
         a.items = wt.items;
@@ -1792,6 +1795,26 @@ int knhip_index_set_sq(knhip_index* idx, const float* vmin, const float* vdiff) 
     idx->has_sq = true;
     idx->xnorm_ready = false;
     return KNHIP_OK;
+}
+
+int knhip_index_set_sq_type(knhip_index* idx, int32_t bits) {
+    if (int rc = check_index(idx)) return rc;
+    if (idx->desc.kind != KNHIP_IVF_SQ8 || !sq_bits_valid(bits)) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "set_sq_type: an IVF_SQ8 index and a code width of 8, 6 or 4 bits");
+    }
+    if (idx->has_data) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "set_sq_type: the index already holds rows");
+    }
+    idx->sq_bits = bits;
+    idx->code_size = sq_code_size(idx->d, bits);
+    return KNHIP_OK;
+}
+
+int32_t knhip_index_get_sq_type(const knhip_index* idx) {
+    if (!idx || idx->desc.kind != KNHIP_IVF_SQ8) {
+        return 0;
+    }
+    return idx->sq_bits;
 }
 
 int knhip_index_set_row_scale(knhip_index* idx, const float* scale, int32_t mode) {

@@ -271,7 +271,7 @@ int encode_rows(const knhip_index* idx, int64_t n, const float* d_x, int64_t* d_
     if (idx->desc.kind == KNHIP_IVF_PQ) {
         HIP_TRY(launch_pq_encode(resid.as<float>(), n, d, idx->desc.pq_m, idx->cb.as<float>(), d_codes, s));
     } else {
-        HIP_TRY(launch_sq8_encode(resid.as<float>(), n, d, idx->sq_trained.as<float>(), d_codes, s));
+        HIP_TRY(launch_sq_encode(resid.as<float>(), n, d, idx->sq_bits, idx->sq_trained.as<float>(), d_codes, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
     return KNHIP_OK;

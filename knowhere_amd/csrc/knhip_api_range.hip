@@ -172,7 +172,8 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
             a.trained = idx->sq_trained.as<float>();
             a.centroids = idx->centroids.as<float>();
             a.d = d;
-            a.nchunk16 = (d + 15) / 16;
+            a.nchunk16 = sq_nchunk16(d, idx->sq_bits);
+            a.bits = idx->sq_bits;
             a.queries = d_q;
             a.coarse_dis = cdis_w;
             a.items = wt.items;

@@ -204,6 +204,7 @@ struct knhip_index {
     bool has_data = false;
     int64_t ntotal = 0;
     int64_t code_size = 0;
+    int sq_bits = 8;      // IVF_SQ8: code width (sq_type SQ8 / SQ6 / SQ4); code_size = sq_code_size(d, sq_bits)
     int64_t id_offset = 0;
     std::vector<int64_t> h_list_len, h_list_row_off;
     DevBuf d_list_len, d_list_row_off, d_list_blk_off;

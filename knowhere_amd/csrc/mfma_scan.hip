@@ -498,24 +498,35 @@ constexpr int MQ_WAVES = 16;
 constexpr int MQ_THREADS = MQ_WAVES * KN_WAVE;
 constexpr int MQ_QT = 32;
 
+template <int BITS>
 __global__ void ms_sq8_norms_kernel(const uint4* __restrict__ rows, int64_t total_blk, int nchunk16, int d,
                                     const float* __restrict__ trained, float* __restrict__ out,
                                     float* __restrict__ out_max) {
+    using W = SqWidth<BITS>;
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     float acc = 0.f;
     const bool live = t < total_blk * 64;
     const int64_t b = live ? (t >> 6) : 0;
     const int r = (int)(t & 63);
     const uint4* p = rows + b * (int64_t)nchunk16 * 64 + r;
-    for (int c = 0; live && c < nchunk16; c++) {
-        const uint4 w = p[(int64_t)c * 64];
-        const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+    const int ngroup = (nchunk16 + W::GROUP_CHUNKS - 1) / W::GROUP_CHUNKS;
+    for (int c = 0; live && c < ngroup; c++) {
+        uint32_t ww[4 * W::GROUP_CHUNKS];
 #pragma unroll
-        for (int e = 0; e < 16; e++) {
-            const int i = c * 16 + e;
+        for (int g = 0; g < W::GROUP_CHUNKS; g++) {
+            const int cc = c * W::GROUP_CHUNKS + g;
+            const uint4 w = (W::GROUP_CHUNKS == 1 || cc < nchunk16) ? p[(int64_t)cc * 64] : make_uint4(0, 0, 0, 0);
+            ww[4 * g + 0] = w.x;
+            ww[4 * g + 1] = w.y;
+            ww[4 * g + 2] = w.z;
+            ww[4 * g + 3] = w.w;
+        }
+#pragma unroll
+        for (int e = 0; e < W::GROUP_DIMS; e++) {
+            const int i = c * W::GROUP_DIMS + e;
             if (i < d) {
-                const float code = (float)((ww[e >> 2] >> (8 * (e & 3))) & 0xffu);
-                const float x = trained[i] + trained[d + i] * ((code + 0.5f) / 255.0f);
+                const float code = (float)sq_group_code<BITS>(ww, e);
+                const float x = trained[i] + trained[d + i] * ((code + 0.5f) / (float)(W::NCODE - 1));
                 acc += x * x;
             }
         }
@@ -533,13 +544,14 @@ __global__ void ms_sq8_norms_kernel(const uint4* __restrict__ rows, int64_t tota
 }
 
 hipError_t launch_ms_sq8_norms(const uint4* rows, int64_t total_blk, int nchunk16, int d, const float* trained,
-                               float* out, float* out_max, hipStream_t s) {
+                               float* out, float* out_max, hipStream_t s, int bits) {
     hipError_t e = hipMemsetAsync(out_max, 0, sizeof(float), s);
     if (e != hipSuccess || total_blk <= 0) {
         return e;
     }
-    hipLaunchKernelGGL(ms_sq8_norms_kernel, dim3((unsigned)((total_blk * 64 + 255) / 256)), dim3(256), 0, s, rows,
-                       total_blk, nchunk16, d, trained, out, out_max);
+    auto kern = bits == 8 ? ms_sq8_norms_kernel<8> : bits == 6 ? ms_sq8_norms_kernel<6> : ms_sq8_norms_kernel<4>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((total_blk * 64 + 255) / 256)), dim3(256), 0, s, rows, total_blk, nchunk16, d,
+                       trained, out, out_max);
     return hipGetLastError();
 }
 
@@ -574,6 +586,7 @@ __device__ __forceinline__ void ms_codes_to_f16(const uint4 w, ms_f16x8& lo8, ms
 // One wave per query: y' = q vdiff / 255 scaled by sc = 2^ex (max |y'| sc in [2^9, 2^10)) and split into halves hi + lo
 // -> qh / ql [nq][ldq] (zero padded to the step multiple); qs[q] = {sc, A, W, sum |y'|, sum (hi + lo), finite?, 0, 0}.
 // The same arithmetic as the in-kernel prologue below.
+template <int BITS>
 __global__ __launch_bounds__(256) void ms_sq8_query_prep_kernel(const float* __restrict__ queries, int64_t nq, int d,
                                                                 int ldq, const float* __restrict__ trained,
                                                                 _Float16* __restrict__ qh, _Float16* __restrict__ ql,
@@ -583,12 +596,14 @@ __global__ __launch_bounds__(256) void ms_sq8_query_prep_kernel(const float* __r
     if (q >= nq) {
         return;
     }
+    constexpr float MS_INV = 1.0f / (float)(SqWidth<BITS>::NCODE - 1);
+    constexpr float MS_XMAX = BITS == 8 ? 1.0f : ((float)SqWidth<BITS>::NCODE - 0.5f) / (float)(SqWidth<BITS>::NCODE - 1);
     const float* vmin = trained;
     const float* vdiff = trained + d;
     const float* qv = queries + q * d;
     float mx = 0.f;
     for (int i = lane; i < d; i += KN_WAVE) {
-        mx = fmaxf(mx, fabsf(qv[i] * vdiff[i] * (1.0f / 255.0f)));
+        mx = fmaxf(mx, fabsf(qv[i] * vdiff[i] * MS_INV));
     }
     for (int off = 32; off > 0; off >>= 1) {
         mx = fmaxf(mx, __shfl_xor(mx, off, KN_WAVE));
@@ -604,16 +619,16 @@ __global__ __launch_bounds__(256) void ms_sq8_query_prep_kernel(const float* __r
         _Float16 h = (_Float16)0.f, l = (_Float16)0.f;
         if (i < d) {
             const float y = qv[i];
-            const float yp = y * vdiff[i] * (1.0f / 255.0f) * sc;
+            const float yp = y * vdiff[i] * MS_INV * sc;
             h = (_Float16)yp;
             l = (_Float16)(yp - (float)h);
-            sA += y * (vmin[i] + 0.5f * vdiff[i] * (1.0f / 255.0f));
-            sW += fabsf(y) * (fabsf(vmin[i]) + fabsf(vdiff[i]));
-            sYp += fabsf(y * vdiff[i] * (1.0f / 255.0f));
+            sA += y * (vmin[i] + 0.5f * vdiff[i] * MS_INV);
+            sW += fabsf(y) * (fabsf(vmin[i]) + MS_XMAX * fabsf(vdiff[i]));
+            sYp += fabsf(y * vdiff[i] * MS_INV);
             sHL += (float)h + (float)l;
         }
-        qh[q * ldq + i] = h;
-        ql[q * ldq + i] = l;
+        qh[q * ldq + sq_operand_pos<BITS>(i)] = h;
+        ql[q * ldq + sq_operand_pos<BITS>(i)] = l;
     }
     sA = ms_wave_sum(sA);
     sW = ms_wave_sum(sW);
@@ -633,17 +648,29 @@ __global__ __launch_bounds__(256) void ms_sq8_query_prep_kernel(const float* __r
 }
 
 hipError_t launch_ms_sq8_query_prep(const float* queries, int64_t nq, int d, int ldq, const float* trained, void* qh,
-                                    void* ql, float* qs, hipStream_t s) {
+                                    void* ql, float* qs, hipStream_t s, int bits) {
     if (nq <= 0) {
         return hipSuccess;
     }
-    hipLaunchKernelGGL(ms_sq8_query_prep_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, queries, nq, d, ldq,
+    auto kern = bits == 8 ? ms_sq8_query_prep_kernel<8> : bits == 6 ? ms_sq8_query_prep_kernel<6> : ms_sq8_query_prep_kernel<4>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, queries, nq, d, ldq,
                        trained, reinterpret_cast<_Float16*>(qh), reinterpret_cast<_Float16*>(ql), qs);
     return hipGetLastError();
 }
 
 // DUMP: as in mscan_flat_kernel; the pessimistic distance is u0 + v (acc - off) with the per-pair constants below.
-template <bool IS_L2, bool DUMP>
+// the code bytes a lane holds for one step: rows lr and lr + 32
+template <int BITS>
+struct MsCodeLoad {
+    uint4 q[2];
+};
+template <>
+struct MsCodeLoad<6> {
+    uint4 q[2];
+    uint2 h[2];
+};
+
+template <bool IS_L2, bool DUMP, int BITS>
 __device__ __forceinline__ void mscan_sq8_unit(const MScanArgs a, const int64_t u, unsigned char* smem) {
     const int lane = lane_id();
     const int wave = threadIdx.x / KN_WAVE;
@@ -654,9 +681,15 @@ __device__ __forceinline__ void mscan_sq8_unit(const MScanArgs a, const int64_t 
     const int64_t blk0 = a.list_blk_off[list];
     const int64_t row_off = a.list_row_off[list];
     const int d = a.d;
-    const int nchunk = a.nchunk; // 16-code chunks
-    const int nstep = a.nstep;   // steps of 32 dims
-    const int ldh = nstep * 32 + 8; // halves per query row: an odd number of 16-byte quads
+    using ST = SqStep<BITS>;
+    constexpr int SD = ST::STEP_DIMS;
+    constexpr float MS_INV = 1.0f / (float)(SqWidth<BITS>::NCODE - 1);
+    // |x_i| <= |vmin_i| + |vdiff_i| (2^BITS - 0.5) / (2^BITS - 1): the last factor is 1.002 for 8 bits (inside the bound's
+    // factor 2, left as it was), 1.008 and 1.033 for 6 and 4 bits
+    constexpr float MS_XMAX = BITS == 8 ? 1.0f : ((float)SqWidth<BITS>::NCODE - 0.5f) / (float)(SqWidth<BITS>::NCODE - 1);
+    const int nchunk = a.nchunk; // 16-byte chunks of a row
+    const int nstep = a.nstep;   // steps of SD dims (8 bits: 32 = two chunks; 4 bits: 64 = two chunks; 6 bits: 64 = three)
+    const int ldh = nstep * SD + 8; // halves per query row: an odd number of 16-byte quads
 
     _Float16* sH = reinterpret_cast<_Float16*>(smem);      // [32][ldh]
     _Float16* sL = sH + MQ_QT * ldh;                       // [32][ldh]
@@ -687,7 +720,7 @@ __device__ __forceinline__ void mscan_sq8_unit(const MScanArgs a, const int64_t 
             float mx = 0.f;
             for (int i = lane; !prepared && i < d; i += KN_WAVE) {
                 const float y = IS_L2 ? (qv[i] - cen[i]) : qv[i];
-                mx = fmaxf(mx, fabsf(y * vdiff[i] * (1.0f / 255.0f)));
+                mx = fmaxf(mx, fabsf(y * vdiff[i] * MS_INV));
             }
             for (int off = 32; off > 0; off >>= 1) {
                 mx = fmaxf(mx, __shfl_xor(mx, off, KN_WAVE));
@@ -708,21 +741,21 @@ __device__ __forceinline__ void mscan_sq8_unit(const MScanArgs a, const int64_t 
                 sHL = o[4];
                 mx = o[5] != 0.f ? 0.f : INFINITY;
             }
-            for (int i = lane; !prepared && i < nstep * 32; i += KN_WAVE) {
+            for (int i = lane; !prepared && i < nstep * SD; i += KN_WAVE) {
                 _Float16 h = (_Float16)0.f, l = (_Float16)0.f;
                 if (i < d) {
                     const float y = IS_L2 ? (qv[i] - cen[i]) : qv[i];
-                    const float yp = y * vdiff[i] * (1.0f / 255.0f) * sc;
+                    const float yp = y * vdiff[i] * MS_INV * sc;
                     h = (_Float16)yp;
                     l = (_Float16)(yp - (float)h);
-                    sA += y * (vmin[i] + 0.5f * vdiff[i] * (1.0f / 255.0f));
-                    sW += fabsf(y) * (fabsf(vmin[i]) + fabsf(vdiff[i])); // >= sum |y_i x_i|
-                    sYp += fabsf(y * vdiff[i] * (1.0f / 255.0f));          // sum |y'_i| (unscaled)
+                    sA += y * (vmin[i] + 0.5f * vdiff[i] * MS_INV);
+                    sW += fabsf(y) * (fabsf(vmin[i]) + MS_XMAX * fabsf(vdiff[i])); // >= sum |y_i x_i|
+                    sYp += fabsf(y * vdiff[i] * MS_INV);          // sum |y'_i| (unscaled)
                     sHL += (float)h + (float)l;
                     sR += y * y;
                 }
-                sH[j * ldh + i] = h;
-                sL[j * ldh + i] = l;
+                sH[j * ldh + sq_operand_pos<BITS>(i)] = h;
+                sL[j * ldh + sq_operand_pos<BITS>(i)] = l;
             }
             if (!prepared) {
                 sA = ms_wave_sum(sA);
@@ -774,7 +807,7 @@ __device__ __forceinline__ void mscan_sq8_unit(const MScanArgs a, const int64_t 
                 }
             }
         } else if (IS_L2 || a.qs == nullptr) {
-            for (int i = lane; i < nstep * 32; i += KN_WAVE) {
+            for (int i = lane; i < nstep * SD; i += KN_WAVE) {
                 sH[j * ldh + i] = (_Float16)0.f;
                 sL[j * ldh + i] = (_Float16)0.f;
             }
@@ -792,7 +825,7 @@ __device__ __forceinline__ void mscan_sq8_unit(const MScanArgs a, const int64_t 
     __syncthreads();
     if (!IS_L2 && a.qs != nullptr) {
         // prepared query operands: the 32 pairs' hi / lo rows are copied into LDS, 16 bytes per thread and turn
-        const int nv = nstep * 4; // 16-byte pieces per row (nstep * 32 halves)
+        const int nv = nstep * (SD / 8); // 16-byte pieces per row (nstep * SD halves)
         const uint4* gh = reinterpret_cast<const uint4*>(a.qh);
         const uint4* gl = reinterpret_cast<const uint4*>(a.ql);
         for (int t = threadIdx.x; t < MQ_QT * nv; t += MQ_THREADS) {
@@ -819,21 +852,33 @@ __device__ __forceinline__ void mscan_sq8_unit(const MScanArgs a, const int64_t 
     }
     const uint4* rows = reinterpret_cast<const uint4*>(a.rows) + blk0 * (int64_t)nchunk * 64;
     // branch-free (see mscan_flat_kernel): clamped re-reads instead of conditionals around the loads
-    auto load_step = [&](int64_t b, int s, uint4 (&A)[2]) {
+    // (a chunk index past the row's last one is clamped: its codes meet query operands that are zero)
+    auto load_step = [&](int64_t b, int s, MsCodeLoad<BITS>(&A)) {
         const int64_t bb = min(b, nblk - 1);
-        const int c = min(2 * s + hi, nchunk - 1);
-        const uint4* p = rows + (bb * nchunk + c) * 64 + lr;
-        A[0] = p[0];
-        A[1] = p[32];
+        if constexpr (BITS == 6) {
+            // 48 bytes = 64 codes per step: this half-wave's 24 bytes are chunk 0 + the low half of chunk 1 (hi = 0) or
+            // the high half of chunk 1 + chunk 2 (hi = 1)
+            const uint4* pq = rows + (bb * nchunk + min(3 * s + 2 * hi, nchunk - 1)) * 64 + lr;
+            const uint2* ph = reinterpret_cast<const uint2*>(rows + (bb * nchunk + min(3 * s + 1, nchunk - 1)) * 64 + lr) + hi;
+            A.q[0] = pq[0];
+            A.q[1] = pq[32];
+            A.h[0] = ph[0];
+            A.h[1] = ph[64]; // (32 rows of 16 bytes further)
+        } else {
+            const int c = min(2 * s + hi, nchunk - 1);
+            const uint4* p = rows + (bb * nchunk + c) * 64 + lr;
+            A.q[0] = p[0];
+            A.q[1] = p[32];
+        }
     };
     // Code loads run THREE steps ahead of the MFMAs that consume them, in four statically rotating register sets
     // (the step loop is flattened over this wave's blocks and unrolled by four: a copy-rotation would make every
     // step wait for the newest load).  At d = 768 one workgroup fills a CU's LDS, so its 16 waves x 3 x 2 KiB in
     // flight are what covers the HBM latency.
-    uint4 A[4][2];
+    MsCodeLoad<BITS> A[4];
     int64_t lb = wave; // load cursor
     int ls = 0;
-    auto issue = [&](uint4 (&dst)[2]) {
+    auto issue = [&](MsCodeLoad<BITS>(&dst)) {
         load_step(lb, ls, dst);
         if (++ls == nstep) {
             ls = 0;
@@ -868,19 +913,48 @@ __device__ __forceinline__ void mscan_sq8_unit(const MScanArgs a, const int64_t 
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(hi == 0 ? xn_next1 : 0.f, bs, z, 0, 0, 0);
         }
     };
-    auto compute = [&](const uint4 (&Ac)[2], int s) {
-        ms_f16x8 Bh[2], Bl[2];
+    auto compute = [&](const MsCodeLoad<BITS>(&Ac), int s) {
+        constexpr int NOP = ST::HALF_OPS;
+        ms_f16x8 Bh[NOP], Bl[NOP];
 #pragma unroll
-        for (int e8 = 0; e8 < 2; e8++) {
-            Bh[e8] = *reinterpret_cast<const ms_f16x8*>(sH + lr * ldh + 32 * s + 16 * hi + 8 * e8);
-            Bl[e8] = *reinterpret_cast<const ms_f16x8*>(sL + lr * ldh + 32 * s + 16 * hi + 8 * e8);
+        for (int e8 = 0; e8 < NOP; e8++) {
+            Bh[e8] = *reinterpret_cast<const ms_f16x8*>(sH + lr * ldh + SD * s + (SD / 2) * hi + 8 * e8);
+            Bl[e8] = *reinterpret_cast<const ms_f16x8*>(sL + lr * ldh + SD * s + (SD / 2) * hi + 8 * e8);
         }
 #pragma unroll
         for (int t = 0; t < 2; t++) {
-            ms_f16x8 Af[2];
-            ms_codes_to_f16(Ac[t], Af[0], Af[1]);
+            ms_f16x8 Af[NOP];
+            if constexpr (BITS == 8) {
+                ms_codes_to_f16(Ac.q[t], Af[0], Af[1]);
+            } else {
+                union {
+                    uint32_t u[4 * NOP];
+                    ms_f16x8 v[NOP];
+                } o;
+                uint32_t D[ST::HALF_DWORDS];
+                const uint4 w = Ac.q[t];
+                if constexpr (BITS == 6) {
+                    const uint2 h2 = Ac.h[t];
+                    D[0] = hi ? h2.x : w.x;
+                    D[1] = hi ? h2.y : w.y;
+                    D[2] = hi ? w.x : w.z;
+                    D[3] = hi ? w.y : w.w;
+                    D[4] = hi ? w.z : h2.x;
+                    D[5] = hi ? w.w : h2.y;
+                } else {
+                    D[0] = w.x;
+                    D[1] = w.y;
+                    D[2] = w.z;
+                    D[3] = w.w;
+                }
+                sq_operands<BITS>(D, o.u);
 #pragma unroll
-            for (int e8 = 0; e8 < 2; e8++) {
+                for (int e8 = 0; e8 < NOP; e8++) {
+                    Af[e8] = o.v[e8];
+                }
+            }
+#pragma unroll
+            for (int e8 = 0; e8 < NOP; e8++) {
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Af[e8], Bh[e8], acc[t], 0, 0, 0);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Af[e8], Bl[e8], acc[t], 0, 0, 0);
             }
@@ -959,13 +1033,13 @@ __device__ __forceinline__ void mscan_sq8_unit(const MScanArgs a, const int64_t 
     }
 }
 
-template <bool IS_L2, bool DUMP, bool LOOP>
+template <bool IS_L2, bool DUMP, bool LOOP, int BITS>
 __global__ __launch_bounds__(MQ_THREADS) void mscan_sq8_kernel(MScanArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int64_t nunits = *a.nunits_dev;
     if (LOOP) { // (see mscan_flat_kernel)
         for (int64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
-            mscan_sq8_unit<IS_L2, DUMP>(a, u, smem);
+            mscan_sq8_unit<IS_L2, DUMP, BITS>(a, u, smem);
             __syncthreads();
         }
     } else {
@@ -976,7 +1050,7 @@ __global__ __launch_bounds__(MQ_THREADS) void mscan_sq8_kernel(MScanArgs a) {
         if (u >= nunits) {
             return;
         }
-        mscan_sq8_unit<IS_L2, DUMP>(a, u, smem);
+        mscan_sq8_unit<IS_L2, DUMP, BITS>(a, u, smem);
     }
 }
 
@@ -1064,7 +1138,8 @@ hipError_t launch_ms_tau(const float* sel_d, int64_t nq, int k, bool is_l2, floa
 constexpr int MF_THREADS = 256;
 constexpr int MF_MLP = 8; // row pieces requested at a time per candidate
 
-template <bool IS_L2, int KIND> // KIND 1: fp32 rows, 2: PQ codes (M = 32, dsub = 4; pq_filter.hip), 3: SQ8
+// KIND 1: fp32 rows, 2: PQ codes (M = 32, dsub = 4; pq_filter.hip), 3: IVF-SQ codes of BITS bits
+template <bool IS_L2, int KIND, int BITS = 8>
 __global__ __launch_bounds__(MF_THREADS) void mscan_finish_kernel(MScanArgs a, const int64_t* __restrict__ keys,
                                                                   const float* __restrict__ coarse_dis, int nprobe,
                                                                   int k, int P_max, float* __restrict__ out_d,
@@ -1072,6 +1147,7 @@ __global__ __launch_bounds__(MF_THREADS) void mscan_finish_kernel(MScanArgs a, c
                                                                   unsigned long long* __restrict__ counters, int pass) {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ float tab[256];
+    static_assert(KIND == 3 || BITS == 8, "the code width belongs to the IVF-SQ finish");
     const int64_t q = blockIdx.x;
     const int tid = threadIdx.x;
     // pass 1: queries that did not overflow are finished; an overflowed query (flag 1) with candidates gets a RETRY:
@@ -1285,7 +1361,9 @@ __global__ __launch_bounds__(MF_THREADS) void mscan_finish_kernel(MScanArgs a, c
     unsigned long long* tie = reinterpret_cast<unsigned long long*>(smem);
     uint32_t* key = reinterpret_cast<uint32_t*>(smem + (size_t)P_max * 8);
     float* sq = reinterpret_cast<float*>(smem + (size_t)P_max * 12);
-    const int dq = KIND == 3 ? a.nchunk * 16 : a.nchunk * 4;
+    using SW = SqWidth<BITS>;
+    const int sq_ngroup = (a.nchunk + SW::GROUP_CHUNKS - 1) / SW::GROUP_CHUNKS;
+    const int dq = KIND == 3 ? sq_ngroup * SW::GROUP_DIMS : a.nchunk * 4;
     float* svmin = sq + dq;
     float* svdiff = svmin + dq;
     for (int i = tid; i < dq; i += MF_THREADS) {
@@ -1295,8 +1373,8 @@ __global__ __launch_bounds__(MF_THREADS) void mscan_finish_kernel(MScanArgs a, c
             svdiff[i] = (i < d) ? a.trained[d + i] : 0.f;
         }
     }
-    if (KIND == 3 && tid < 256) {
-        tab[tid] = __fdiv_rn((float)tid + 0.5f, 255.0f); // Codec8bit::decode_component
+    if (KIND == 3 && tid < SW::NCODE) {
+        tab[tid] = sq_decode_xi<BITS>(tid); // Codec8bit / Codec6bit / Codec4bit::decode_component
     }
     for (int e = tid; e < k; e += MF_THREADS) { // the running top-k starts empty
         key[e] = 0xffffffffu;
@@ -1394,6 +1472,50 @@ __global__ __launch_bounds__(MF_THREADS) void mscan_finish_kernel(MScanArgs a, c
                         acc = fadd_x(acc, t);
                     }
                     if (a.pq_lut_mode != PQ_LUT_RESIDUAL) {
+                        acc = fadd_x(coarse_dis[q * nprobe + slot], acc);
+                    }
+                } else if (BITS != 8) {
+                    // packed 6- and 4-bit codes: whole groups (three chunks = 64 dims / one chunk = 32 dims), the exact
+                    // kernel's sequence (sq_scan.hip)
+                    constexpr int GC = SW::GROUP_CHUNKS, GD = SW::GROUP_DIMS;
+                    constexpr int NG = BITS == 6 ? 2 : 4; // groups requested at a time
+                    const uint4* p = reinterpret_cast<const uint4*>(a.rows) + blk * (int64_t)a.nchunk * 64 + r;
+                    const float* cen = a.centroids + list * d;
+                    for (int g0 = 0; g0 < sq_ngroup; g0 += NG) {
+                        uint4 wv[NG * GC];
+#pragma unroll
+                        for (int u = 0; u < NG * GC; u++) {
+                            wv[u] = p[(int64_t)min(g0 * GC + u, a.nchunk - 1) * 64];
+                        }
+#pragma unroll
+                        for (int gu = 0; gu < NG; gu++) {
+                            const int g = g0 + gu;
+                            if (g < sq_ngroup) {
+                                uint32_t ww[4 * GC];
+#pragma unroll
+                                for (int c1 = 0; c1 < GC; c1++) {
+                                    const bool in = g * GC + c1 < a.nchunk; // (a chunk past the row's last one is padding)
+                                    ww[4 * c1 + 0] = in ? wv[gu * GC + c1].x : 0u;
+                                    ww[4 * c1 + 1] = in ? wv[gu * GC + c1].y : 0u;
+                                    ww[4 * c1 + 2] = in ? wv[gu * GC + c1].z : 0u;
+                                    ww[4 * c1 + 3] = in ? wv[gu * GC + c1].w : 0u;
+                                }
+#pragma unroll
+                                for (int e2 = 0; e2 < GD; e2++) {
+                                    const int i = g * GD + e2;
+                                    const uint32_t code = sq_group_code<BITS>(ww, e2);
+                                    const float x = fadd_x(svmin[i], fmul_x(tab[code], svdiff[i]));
+                                    if (IS_L2) {
+                                        const float y = (i < d) ? fsub_x(sq[i], cen[i]) : 0.f;
+                                        acc = l2_step(acc, y, x);
+                                    } else {
+                                        acc = ip_step(acc, sq[i], x);
+                                    }
+                                }
+                            }
+                        }
+                    }
+                    if (!IS_L2) {
                         acc = fadd_x(coarse_dis[q * nprobe + slot], acc);
                     }
                 } else {
@@ -1543,21 +1665,27 @@ int mscan_queries_per_unit(int kind, bool sample) {
     return kind == 1 ? (sample ? 32 : MS_QT) : kind == 2 ? 8 : MQ_QT; // (kind 2: pq_filter.hip, 8 queries per LUT)
 }
 
-size_t mscan_sq8_smem(int nstep) {
-    return (size_t)2 * MQ_QT * (nstep * 32 + 8) * 2 + (size_t)MQ_QT * 28;
+size_t mscan_sq8_smem(int nstep, int bits) {
+    return (size_t)2 * MQ_QT * (nstep * (bits == 8 ? 32 : 64) + 8) * 2 + (size_t)MQ_QT * 28;
 }
 
 hipError_t launch_mscan_sq8(const MScanArgs& a, bool is_l2, int64_t units_bound, hipStream_t s) {
     if (units_bound <= 0) {
         return hipSuccess;
     }
-    const size_t sm = mscan_sq8_smem(a.nstep);
-    const bool dump = a.dump != nullptr;
-    auto kern = is_l2 ? (dump ? mscan_sq8_kernel<true, true, false> : mscan_sq8_kernel<true, false, false>)
-                      : (dump ? mscan_sq8_kernel<false, true, false> : mscan_sq8_kernel<false, false, false>);
-    if (a.unit_loop && !dump) { // the retry round's one-query units
-        kern = is_l2 ? mscan_sq8_kernel<true, false, true> : mscan_sq8_kernel<false, false, true>;
+    const int bits = a.sq_bits == 0 ? 8 : a.sq_bits;
+    if (!sq_bits_valid(bits)) {
+        return hipErrorInvalidValue;
     }
+    const size_t sm = mscan_sq8_smem(a.nstep, bits);
+    const bool dump = a.dump != nullptr;
+    const bool loop = a.unit_loop && !dump; // the retry round's one-query units
+#define MQ_PICK(B_)                                                                                              \
+    (loop ? (is_l2 ? mscan_sq8_kernel<true, false, true, B_> : mscan_sq8_kernel<false, false, true, B_>)         \
+          : is_l2 ? (dump ? mscan_sq8_kernel<true, true, false, B_> : mscan_sq8_kernel<true, false, false, B_>)  \
+                  : (dump ? mscan_sq8_kernel<false, true, false, B_> : mscan_sq8_kernel<false, false, false, B_>))
+    auto kern = bits == 8 ? MQ_PICK(8) : bits == 6 ? MQ_PICK(6) : MQ_PICK(4);
+#undef MQ_PICK
     if (sm > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
@@ -1618,11 +1746,15 @@ hipError_t launch_mscan_finish(const MScanArgs& a, int kind, bool is_l2, const i
         return hipSuccess;
     }
     const int P_max = mscan_finish_pmax(a.cap, k);
-    const int dq = kind == 3 ? a.nchunk * 16 : a.nchunk * 4;
+    const int bits = a.sq_bits == 0 ? 8 : a.sq_bits;
+    if (kind == 3 && !sq_bits_valid(bits)) {
+        return hipErrorInvalidValue;
+    }
+    const int dq = kind == 3 ? sq_dpad(a.d, bits) : a.nchunk * 4;
     const size_t sm = (size_t)P_max * 12 + (size_t)dq * 4 * (kind == 3 ? 3 : 1);
-#define MF_LAUNCH(L2_, KIND_)                                                                                   \
+#define MF_LAUNCH(L2_, KIND_, ...)                                                                              \
     do {                                                                                                        \
-        auto kern = mscan_finish_kernel<L2_, KIND_>;                                                            \
+        auto kern = mscan_finish_kernel<L2_, KIND_, ##__VA_ARGS__>;                                             \
         if (sm > 48 * 1024) {                                                                                   \
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                             \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);            \
@@ -1635,8 +1767,12 @@ hipError_t launch_mscan_finish(const MScanArgs& a, int kind, bool is_l2, const i
         if (is_l2) MF_LAUNCH(true, 1); else MF_LAUNCH(false, 1);
     } else if (kind == 2) {
         if (is_l2) MF_LAUNCH(true, 2); else MF_LAUNCH(false, 2);
-    } else {
+    } else if (bits == 8) {
         if (is_l2) MF_LAUNCH(true, 3); else MF_LAUNCH(false, 3);
+    } else if (bits == 6) {
+        if (is_l2) MF_LAUNCH(true, 3, 6); else MF_LAUNCH(false, 3, 6);
+    } else {
+        if (is_l2) MF_LAUNCH(true, 3, 4); else MF_LAUNCH(false, 3, 4);
     }
 #undef MF_LAUNCH
     return hipGetLastError();

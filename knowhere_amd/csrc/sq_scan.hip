@@ -33,12 +33,14 @@ int sq_scan_qg(int k) {
 
 // one work item (`item_or_block` is the item when a.item_loop is set, else the block index that xcd_item maps to an
 // item).  Every exit is workgroup-uniform.
-template <bool IS_L2, int QG, int R>
+template <bool IS_L2, int QG, int R, int BITS>
 __device__ __forceinline__ void sq_scan_item(const SqScanArgs& a, const int64_t item_or_block, unsigned char* smem,
                                              float* tab) {
     const int lane = lane_id();
     const int wave = threadIdx.x / KN_WAVE;
-    const int dpad = a.nchunk16 * 16;
+    using W = SqWidth<BITS>;
+    const int ngroup = (a.nchunk16 + W::GROUP_CHUNKS - 1) / W::GROUP_CHUNKS;
+    const int dpad = ngroup * W::GROUP_DIMS;
 
     const int64_t nitems = *a.nitems_dev;
     int64_t item;
@@ -73,8 +75,8 @@ __device__ __forceinline__ void sq_scan_item(const SqScanArgs& a, const int64_t 
     float* sy = reinterpret_cast<float*>(smem);
     float* svmin = sy + QG * dpad;
     float* svdiff = svmin + dpad;
-    if (threadIdx.x < 256) {
-        tab[threadIdx.x] = __fdiv_rn((float)threadIdx.x + 0.5f, 255.0f);
+    if (threadIdx.x < W::NCODE) {
+        tab[threadIdx.x] = sq_decode_xi<BITS>(threadIdx.x);
     }
     for (int t = threadIdx.x; t < QG * dpad; t += SQ_THREADS) {
         const int j = t / dpad, i = t % dpad;
@@ -124,13 +126,22 @@ __device__ __forceinline__ void sq_scan_item(const SqScanArgs& a, const int64_t 
         }
         constexpr int UF = QG <= 2 ? 4 : 1; // (few-query items: keep several code loads in flight)
 #pragma unroll UF
-        for (int c = 0; c < a.nchunk16; c++) {
-            const uint4 w = p[(int64_t)c * 64];
-            const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+        for (int c = 0; c < ngroup; c++) {
+            uint32_t ww[4 * W::GROUP_CHUNKS];
 #pragma unroll
-            for (int e = 0; e < 16; e++) {
-                const uint32_t code = (ww[e >> 2] >> (8 * (e & 3))) & 0xffu;
-                const int i = c * 16 + e;
+            for (int g = 0; g < W::GROUP_CHUNKS; g++) {
+                // (6 bits: the row's last group may own fewer than three chunks; the missing ones are padding)
+                const int cc = c * W::GROUP_CHUNKS + g;
+                const uint4 w = (W::GROUP_CHUNKS == 1 || cc < a.nchunk16) ? p[(int64_t)cc * 64] : make_uint4(0, 0, 0, 0);
+                ww[4 * g + 0] = w.x;
+                ww[4 * g + 1] = w.y;
+                ww[4 * g + 2] = w.z;
+                ww[4 * g + 3] = w.w;
+            }
+#pragma unroll
+            for (int e = 0; e < W::GROUP_DIMS; e++) {
+                const uint32_t code = sq_group_code<BITS>(ww, e);
+                const int i = c * W::GROUP_DIMS + e;
                 const float xi = tab[code];
                 const float x = fadd_x(svmin[i], fmul_x(xi, svdiff[i]));
 #pragma unroll
@@ -234,23 +245,23 @@ __device__ __forceinline__ void sq_scan_item(const SqScanArgs& a, const int64_t 
     }
 }
 
-template <bool IS_L2, int QG, int R>
+template <bool IS_L2, int QG, int R, int BITS>
 __global__ __launch_bounds__(SQ_THREADS) void sq_scan_kernel(SqScanArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ float tab[256]; // (c + 0.5f) / 255.0f, correctly rounded
+    __shared__ float tab[SqWidth<BITS>::NCODE]; // (c + 0.5f) / (2^BITS - 1), correctly rounded
     if (a.item_loop) {
         // a fixed grid walks an item table whose size only the device knows (mfma_scan.hip fallback)
         const int64_t nitems = *a.nitems_dev;
         for (int64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
-            sq_scan_item<IS_L2, QG, R>(a, item, smem, tab);
+            sq_scan_item<IS_L2, QG, R, BITS>(a, item, smem, tab);
             __syncthreads();
         }
         return;
     }
-    sq_scan_item<IS_L2, QG, R>(a, blockIdx.x, smem, tab);
+    sq_scan_item<IS_L2, QG, R, BITS>(a, blockIdx.x, smem, tab);
 }
 
-// AoS codes [len][d] (sorted by list) -> interleaved blocks
+// AoS codes [len][d bytes] (sorted by list; d = the packed code size for 6- and 4-bit codes) -> interleaved blocks
 __global__ void sq_interleave_kernel(const uint8_t* __restrict__ codes,
                                      const int64_t* __restrict__ list_row_off,
                                      const int64_t* __restrict__ list_len,
@@ -290,7 +301,12 @@ hipError_t launch_sq_scan(const SqScanArgs& a, bool is_l2, int64_t grid, hipStre
     if (!a.item_loop) {
         grid = (grid + 7) / 8 * 8; // (xcd_item spreads the items over the blocks [0, round_up(nitems, 8)))
     }
-    const int dpad = a.nchunk16 * 16;
+    const int bits = a.bits == 0 ? 8 : a.bits;
+    if (!sq_bits_valid(bits)) {
+        return hipErrorInvalidValue;
+    }
+    const int gch = bits == 6 ? 3 : 1;
+    const int dpad = (a.nchunk16 + gch - 1) / gch * (gch * 128 / bits);
     const int k = a.k;
     if (k > KN_MAX_K) {
         return hipErrorInvalidValue;
@@ -302,7 +318,8 @@ hipError_t launch_sq_scan(const SqScanArgs& a, bool is_l2, int64_t grid, hipStre
         const size_t mbytes =                                                                      \
             (((size_t)qr * SQ_WAVES * k * 4 + 7) & ~(size_t)7) + (size_t)qr * SQ_WAVES * k * 8;    \
         const size_t sm = std::max(ybytes, mbytes);                                                \
-        auto kern = sq_scan_kernel<L2_, QG_, R_>;                                                  \
+        auto kern = bits == 8 ? sq_scan_kernel<L2_, QG_, R_, 8>                                    \
+                  : bits == 6 ? sq_scan_kernel<L2_, QG_, R_, 6> : sq_scan_kernel<L2_, QG_, R_, 4>;                                                 \
         if (sm > 48 * 1024) {                                                                      \
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
@@ -337,10 +354,11 @@ hipError_t launch_sq_scan(const SqScanArgs& a, bool is_l2, int64_t grid, hipStre
 
 hipError_t launch_sq_interleave(const uint8_t* codes, const int64_t* list_row_off,
                                 const int64_t* list_len, const int64_t* list_blk_off, int64_t nlist,
-                                int d, uint4* out, hipStream_t s) {
+                                int64_t code_size, uint4* out, hipStream_t s) {
     if (nlist <= 0) {
         return hipSuccess;
     }
+    const int d = (int)code_size; // (the kernel moves bytes: one per dimension for 8-bit codes)
     const int nchunk16 = (d + 15) / 16;
     const unsigned gy = (unsigned)std::min<int64_t>(nlist, 32768);
     const unsigned gz = (unsigned)((nlist + gy - 1) / gy);

@@ -345,6 +345,7 @@ class HipIndexNode : public IndexNode {
             nlist_ = c.nlist.value();
             if (nlist_ * 39 > rows) nlist_ = std::max<int64_t>(1, rows / 39);
             default_nprobe_ = c.nprobe.value_or(8);
+            wire_nprobe_ = 1;
         }
         if constexpr (Kind == KNHIP_IVF_PQ) {
             // m = 0: the backend picks, as cuVS does for pq_dim = 0 (about dim / 2): the largest m with a fast kernel (8,
@@ -368,6 +369,22 @@ class HipIndexNode : public IndexNode {
             if (!fits(m_)) return Status::invalid_args;
             nbits_ = c.nbits.value_or(8);
             if (nbits_ < 1 || nbits_ > 8) return Status::invalid_args;
+        }
+        if constexpr (Kind == KNHIP_IVF_SQ8) {
+            // sq_type (ivf_config.h:249-311, WhetherAcceptableSQType; IndexIvfFactory::create_for_sq, ivf_wrapper.cc:191-232):
+            // sq4 / sq6 / sq8 in any letter case -> QT_4bit / QT_6bit / QT_8bit of a residual IndexIVFScalarQuantizer
+            std::string t = c.sq_type.value_or("SQ8");
+            for (auto& ch : t) ch = (char)std::tolower((unsigned char)ch);
+            if (t == "sq8") {
+                sq_bits_ = 8;
+            } else if (t == "sq6") {
+                sq_bits_ = 6;
+            } else if (t == "sq4") {
+                sq_bits_ = 4;
+            } else {
+                LOG_KNOWHERE_ERROR_ << TypeName() << ": invalid sq_type " << c.sq_type.value() << " (sq4 / sq6 / sq8)";
+                return Status::invalid_args;
+            }
         }
         if constexpr (Kind == KNHIP_IVF_PQ || Kind == KNHIP_IVF_SQ8) {
             // a refine index is built iff `refine` AND `refine_type` are given (ivf_wrapper.cc:170, :214).  refine_type
@@ -869,7 +886,9 @@ class HipIndexNode : public IndexNode {
         } else {
             x.fourcc = Kind == KNHIP_IVF_FLAT ? FourCC("IwFl") : Kind == KNHIP_IVF_PQ ? FourCC("IwPQ") : FourCC("IwSq");
             x.nlist = (uint64_t)nlist_;
-            x.nprobe = (uint64_t)default_nprobe_;
+            // IndexIVF::nprobe as the reference's node leaves it: it never sets the field (every search passes its nprobe in
+            // IVFSearchParameters, ivf.cc:908-1150), so an index it built carries faiss's 1 and a loaded one what it was read with
+            x.nprobe = wire_nprobe_;
             x.quantizer.fourcc = flat_cc;
             fill_hdr(x.quantizer.hdr, nlist_, false);
             x.quantizer.xb.resize((size_t)nlist_ * dim_);
@@ -884,10 +903,10 @@ class HipIndexNode : public IndexNode {
                 x.pq_centroids.resize(((size_t)1 << nbits_) * dim_);
                 if ((rc = knhip_index_get_pq(first, x.pq_centroids.data()))) return ToStatus(rc);
             } else if constexpr (Kind == KNHIP_IVF_SQ8) {
-                x.sq_qtype = 0;      // ScalarQuantizer::QT_8bit
+                x.sq_qtype = sq_bits_ == 4 ? 1 : sq_bits_ == 6 ? 6 : 0;  // ScalarQuantizer::QT_4bit / QT_6bit / QT_8bit
                 x.sq_rangestat = 0;  // RS_minmax
                 x.sq_d = (uint64_t)dim_;
-                x.sq_code_size = (uint64_t)dim_;
+                x.sq_code_size = (uint64_t)CodeSize();
                 x.sq_trained.resize((size_t)2 * dim_);
                 if ((rc = knhip_index_get_sq(first, x.sq_trained.data(), x.sq_trained.data() + dim_))) return ToStatus(rc);
             }
@@ -1014,12 +1033,17 @@ class HipIndexNode : public IndexNode {
                 return Status::not_implemented;
             // (PQ codes on the wire: M indices of nbits bits as a little-endian bit string, ProductQuantizer.cpp:69)
             const uint64_t want_cs = Kind == KNHIP_IVF_FLAT ? (uint64_t)d * 4
-                                     : Kind == KNHIP_IVF_PQ ? (x.pq_M * x.pq_nbits + 7) / 8 : (uint64_t)d;
+                                     : Kind == KNHIP_IVF_PQ ? (x.pq_M * x.pq_nbits + 7) / 8
+                                     : x.sq_qtype == 1      ? ((uint64_t)d + 1) / 2      // QT_4bit
+                                     : x.sq_qtype == 6      ? ((uint64_t)d * 6 + 7) / 8  // QT_6bit
+                                                            : (uint64_t)d;
             if (Kind == KNHIP_IVF_PQ && (x.pq_d != (uint64_t)d || d % (int64_t)x.pq_M != 0 ||
                                           x.pq_centroids.size() != ((size_t)1 << x.pq_nbits) * d))
                 return Status::invalid_serialized_index_type;
-            if (Kind == KNHIP_IVF_SQ8 && (x.sq_qtype != 0 || !x.by_residual)) return Status::not_implemented;
-            if (Kind == KNHIP_IVF_SQ8 && (x.sq_d != (uint64_t)d || x.sq_code_size != (uint64_t)d ||
+            // (sq_type: QT_8bit 0, QT_4bit 1, QT_6bit 6; the uniform, fp16, bf16 and direct types are not list codes we scan)
+            if (Kind == KNHIP_IVF_SQ8 && ((x.sq_qtype != 0 && x.sq_qtype != 1 && x.sq_qtype != 6) || !x.by_residual))
+                return Status::not_implemented;
+            if (Kind == KNHIP_IVF_SQ8 && (x.sq_d != (uint64_t)d || x.sq_code_size != want_cs ||
                                            x.sq_trained.size() != 2 * (size_t)d))
                 return Status::invalid_serialized_index_type;
             if (Kind != KNHIP_IVF_FLAT && x.code_size != want_cs) return Status::invalid_serialized_index_type;
@@ -1092,8 +1116,10 @@ class HipIndexNode : public IndexNode {
         dim_ = d;
         nlist_ = (int64_t)x.nlist;
         if (x.nprobe >= 1 && x.nprobe <= 65536) default_nprobe_ = (int64_t)x.nprobe;  // the index's default nprobe
+        wire_nprobe_ = x.nprobe;
         m_ = (int64_t)x.pq_M;
         nbits_ = Kind == KNHIP_IVF_PQ ? (int64_t)x.pq_nbits : 8;
+        sq_bits_ = Kind != KNHIP_IVF_SQ8 ? 8 : x.sq_qtype == 1 ? 4 : x.sq_qtype == 6 ? 6 : 8;
         has_refine_ = x.has_refine;
         refine_rows_type_ = !(x.has_refine && x.refine_is_sq) ? 0
                             : x.refine_sq.qtype == 4          ? KNHIP_ROWS_FP16
@@ -1288,7 +1314,7 @@ class HipIndexNode : public IndexNode {
     }
     int64_t
     CodeSize() const {
-        return Kind == KNHIP_IVF_FLAT ? dim_ * 4 : (Kind == KNHIP_IVF_PQ ? (m_ * nbits_ + 7) / 8 : dim_);
+        return Kind == KNHIP_IVF_FLAT ? dim_ * 4 : (Kind == KNHIP_IVF_PQ ? (m_ * nbits_ + 7) / 8 : (dim_ * sq_bits_ + 7) / 8);
     }
     // a second device-resident store of the raw rows: IndexRefineFlat only (GetVectorByIds of IVF_FLAT is served from the
     // index's own rows through knhip_index_get_vectors' direct map)
@@ -1370,7 +1396,11 @@ class HipIndexNode : public IndexNode {
                 desc.pq_m = (int32_t)m_;
                 desc.pq_nbits = (int32_t)nbits_;
             }
-            if (int rc = knhip_index_create(&desc, &sh_[r].idx.p)) {
+            int rc = knhip_index_create(&desc, &sh_[r].idx.p);
+            if constexpr (Kind == KNHIP_IVF_SQ8) {
+                if (rc == KNHIP_OK && sq_bits_ != 8) rc = knhip_index_set_sq_type(sh_[r].idx.p, (int32_t)sq_bits_);
+            }
+            if (rc) {
                 DropShards();
                 return ToStatus(rc);
             }
@@ -1581,7 +1611,9 @@ class HipIndexNode : public IndexNode {
     std::vector<float> row_scale_by_id_;  // StoredNormCosine(): FLAT inverse L2 norms, IVF_FLAT L2 norms, by row id
     std::string metric_name_ = metric::L2;
     int64_t dim_ = 0, nlist_ = 0, m_ = 0, default_nprobe_ = 8;
+    uint64_t wire_nprobe_ = 1;  // the nprobe field of the serialized IVF header (Serialize)
     int64_t nbits_ = 8;  // IVF_PQ: code width (1 .. 8)
+    int64_t sq_bits_ = 8;  // IVF_SQ8: code width of sq_type (SQ8 / SQ6 / SQ4)
     std::vector<Shard> sh_;        // one entry: the whole index on one device; several: list- (FLAT: row-) sharded
     GroupHandle group_;            // several shards: the exchange + merge host (include/knhip_shards.h)
     std::vector<int32_t> owner_;   // several shards, IVF kinds: list -> shard

@@ -190,8 +190,8 @@ struct HipIvfSqConfig : public IvfSqConfig {
         if (param_type == PARAM_TYPE::TRAIN && sq_type.has_value()) {
             std::string t = sq_type.value();
             for (auto& c : t) c = (char)std::toupper((unsigned char)c);
-            if (t != "SQ8") {
-                if (err_msg) *err_msg = "GPU_HIP_IVF_SQ8 supports sq_type SQ8 only";
+            if (t != "SQ8" && t != "SQ6" && t != "SQ4") {
+                if (err_msg) *err_msg = "GPU_HIP_IVF_SQ8 supports sq_type SQ4, SQ6 and SQ8";
                 return Status::invalid_args;
             }
         }

@@ -40,15 +40,28 @@ def _bitset_nbits(bitset, nbits):
 
 class GpuIndex:
     def __init__(self, kind, metric, dim, nlist=0, pq_m=0, pq_nbits=8, device=0,
-                 precomputed_table_max_bytes=0):
+                 precomputed_table_max_bytes=0, sq_type=8):
+        """sq_type: IVF_SQ8 only, the code width of the list codes in bits -- 8 (default), 6 or 4, the reference's
+        sq_type SQ8 / SQ6 / SQ4; list codes are the reference's bytes, _lib.sq_code_size(dim, sq_type) per row"""
         self.L = _lib.load()
         self.kind, self.metric, self.dim, self.nlist, self.pq_m = kind, metric, dim, nlist, pq_m
         self.pq_nbits = pq_nbits
         self.device = device
+        self.sq_type = int(sq_type)
+        if self.sq_type != 8 and (kind != IVF_SQ8 or self.sq_type not in (6, 4)):
+            raise ValueError("sq_type: 8, 6 or 4, and other than 8 on an IVF_SQ8 index only")
         d = _lib.Desc(kind, metric, dim, device, nlist, pq_m, pq_nbits, precomputed_table_max_bytes)
         h = C.c_void_p()
         check(self.L.knhip_index_create(C.byref(d), C.byref(h)))
         self.h = h
+        if self.sq_type != 8:
+            check(self.L.knhip_index_set_sq_type(self.h, self.sq_type))
+
+    @property
+    def code_size(self):
+        """bytes per row of the host-side list codes (add_lists / get_lists)"""
+        return {BRUTE_FORCE: 4 * self.dim, IVF_FLAT: 4 * self.dim, IVF_PQ: (self.pq_m * self.pq_nbits + 7) // 8,
+                IVF_SQ8: _lib.sq_code_size(self.dim, self.sq_type)}[self.kind]
 
     def close(self):
         if getattr(self, "h", None):
@@ -109,7 +122,8 @@ class GpuIndex:
         """ix: any object with the fields of oracle.binding.IndexData (duck typed; the product does
         not import the oracle)."""
         kind = {0: BRUTE_FORCE, 1: IVF_FLAT, 2: IVF_PQ, 3: IVF_SQ8}[ix.kind]
-        g = cls(kind, ix.metric, ix.d, ix.nlist, ix.M, ix.nbits, device, precomputed_table_max_bytes)
+        g = cls(kind, ix.metric, ix.d, ix.nlist, ix.M, ix.nbits, device, precomputed_table_max_bytes,
+                sq_type=getattr(ix, "sq_type", 8))
         if kind == BRUTE_FORCE:
             g.add_vectors(ix.base)
             return g
@@ -167,7 +181,7 @@ class GpuIndex:
         """-> (assign int64 [n], codes uint8 [n, code_size]) device tensors"""
         import torch
         n = x_t.shape[0]
-        cs = {IVF_FLAT: 4 * self.dim, IVF_PQ: self.pq_m, IVF_SQ8: self.dim}[self.kind]
+        cs = {IVF_FLAT: 4 * self.dim, IVF_PQ: self.pq_m, IVF_SQ8: _lib.sq_code_size(self.dim, self.sq_type)}[self.kind]
         a = torch.empty(n, dtype=torch.int64, device=x_t.device)
         c = torch.empty((n, cs), dtype=torch.uint8, device=x_t.device)
         s = torch.cuda.current_stream(x_t.device).cuda_stream
@@ -196,7 +210,7 @@ class GpuIndex:
         n = int(sizes.sum())
         # (IVF_PQ: the reference's code bytes -- pq_m indices of nbits bits as a little-endian bit string; the DEVICE side
         # entry points -- encode_device, set_lists_device -- speak one byte per sub-quantizer)
-        cs = {IVF_FLAT: 4 * self.dim, IVF_PQ: (self.pq_m * self.pq_nbits + 7) // 8, IVF_SQ8: self.dim}[self.kind]
+        cs = self.code_size
         codes = np.empty((n, cs), np.uint8)
         ids = np.empty(n, np.int64)
         check(self.L.knhip_index_get_lists(self.h, _np_ptr(codes), _np_ptr(ids)))

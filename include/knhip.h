@@ -47,6 +47,7 @@
  * KNHIP_TIES=canonical skips it and returns the canonical k: graph capture, or callers that do not care).
  * Conditions: the ids of every list ascend in storage order -- what IvfIndexNode::Add produces (ids are the running
  * row numbers); knhip_index_add_lists re-sorts a list that does not, and ties inside it are then taken in id order.
+ * k above 1024 (the large-k path, see "search"): the IVF kinds follow the rule at every k up to KNHIP_MAX_K.
  * Not covered (canonical answer): k = 1024; BRUTE_FORCE with k >= 100 (the reference switches to a reservoir,
  * impl/ResultHandler.h:719-728).  A list-sharded index returns the same answer as one index: the rule is applied once, after
  * the merge, over all shards' candidates (knhip_search_canonical_device .. knhip_tie_resolve_device below,
@@ -71,8 +72,11 @@ extern "C" {
  * group and the torch.distributed host agree); value 3 of the profile field pq_filter_form: the decode form of the IVF-PQ prefilter;
  * pq_nbits 1 .. 8 (host-side list codes in the reference's bit-string form).
  * Additive since 9 (new functions only, no structure touched, the version stays 9): the AnnIterator, knhip_iter_*.
+ * Additive since 9: KNHIP_MAX_K, knhip_select_ordered_device (search and refine with 1024 < k <= 16384).
  * Callers compare knhip_abi_version() with the header they were built against. */
 #define KNHIP_ABI_VERSION 9
+/* Largest k of a search and largest k_base of a refine (additive since 9: the large-k path, knhip_select_ordered_device). */
+#define KNHIP_MAX_K 16384
 
 typedef struct knhip_index knhip_index;
 
@@ -322,14 +326,30 @@ void knhip_iter_destroy(knhip_iter* it);
  * nprobe is clamped to nlist (thirdparty/faiss/faiss/IndexIVF.cpp:321-322); ignored for
  * BRUTE_FORCE.  Thread-safe for concurrent calls on one index (every call takes its own scratch and stream).
  * The *_device entry points below share one scratch per stream: calls on the SAME stream are serialised inside
- * the library while they enqueue. */
+ * the library while they enqueue.
+ * k <= KNHIP_MAX_K.  Up to 1024 the search keeps nprobe partial lists of k results per query.  Above it (the large-k path,
+ * one index; every knhip_search* / *_preassigned_device entry point) every exact distance of the probed lists is written in
+ * scan order into a compact row per query -- 4 bytes per row of the query's probed lists, each list padded to 64 rows, the
+ * queries in rounds of at most 2 GiB of such rows (KNHIP_LARGEK_ROUND_KB) -- and one ordered top-k per row selects the
+ * reference heap's k results (plus 16 bytes x the next power of two >= k of sort scratch per query of a round).  The host
+ * reads the batch's coarse keys once to lay the rows out, so such a search cannot be captured in a graph.  The IVF kinds are
+ * exact WITH ties at any such k, k = 16384 included (the path sees every probed row: no (k + 1)-th result is needed, no tie
+ * licence is taken); for the inner product that includes the coarse quantizer's own boundary -- among centroids tied at the
+ * nprobe-th distance this path probes the ones the reference's coarse heap keeps (the earliest), where the coarse stage of
+ * k <= 1024 and knhip_coarse_search_device return the canonical ones.  BRUTE_FORCE runs the full distance matrix in query rounds and returns the canonical answer (the
+ * reference's reservoir for k >= 100 keeps its licence); both cosine modes apply.  knhip_search_canonical_device, the
+ * knhip_tie_* steps, knhip_merge_topk_* and the shard group stay at k <= 1024 and refuse more. */
 int knhip_search(const knhip_index* idx, const float* queries, int64_t nq, int32_t k,
                  int32_t nprobe, const uint8_t* bitset, int64_t bitset_nbits, int64_t* out_ids,
                  float* out_dist);
 /* Search k_base candidates, re-rank them exactly against the raw fp32 rows held by `raw` (a BRUTE_FORCE knhip_index on
  * the same device whose row r is vector id r + id_offset) and return the k best: faiss::IndexRefine::search
  * (thirdparty/faiss/faiss/IndexRefine.cpp:61-140), Knowhere's build-time `refine` + search-time `refine_k`
- * (src/index/ivf/ivf.cc:673-700, 1073-1103).  Queries go up once, candidates never leave the device. */
+ * (src/index/ivf/ivf.cc:673-700, 1073-1103).  Queries go up once, candidates never leave the device.
+ * k <= k_base <= KNHIP_MAX_K (here and in knhip_search_refine_rows, knhip_refine_device, knhip_refine_rows_device,
+ * knhip_refine_*distances_device, knhip_refine_select_device).  k_base above 1024: the candidates' distances are written
+ * to a [nq][k_base] scratch and the ordered top-k (knhip_select_ordered_device's kernel) applies reorder_2_heaps' rule in
+ * candidate order; the *_device forms then allocate that scratch per call and drain the stream before they return. */
 int knhip_search_refine(const knhip_index* idx, const knhip_index* raw, const float* queries, int64_t nq, int32_t k,
                         int32_t k_base, int32_t nprobe, const uint8_t* bitset, int64_t bitset_nbits, int64_t* out_ids,
                         float* out_dist);
@@ -486,6 +506,21 @@ int knhip_refine_select_device(int32_t metric, int64_t nq, const int64_t* d_cand
 /* host form of the selection (distances already combined) */
 int knhip_refine_select_host(int32_t metric, int64_t nq, const int64_t* cand_ids, const float* dist, int32_t k_base, int32_t k,
                              float* out_dist, int64_t* out_ids);
+
+/* ---- ordered top-k of rows of distances given in ARRIVAL order: the reference heap's k results, any k <= KNHIP_MAX_K ----
+ * The selection step of the large-k search and refine, exposed as the tie steps are.  Row q = d_dist + q * row_stride, its
+ * first d_row_len[q] (<= row_stride < 2^31) entries in the order the reference would have met them; an entry is absent when
+ * its distance is not better than the neutral value (+FLT_MAX for L2, -FLT_MAX for IP, NaN: what the dump-mode scans
+ * write for filtered rows) or when its id is negative.  d_ids: [nq][row_stride] the ids of the entries, or NULL (id =
+ * column).  Output [nq][k] in heap_reorder order (L2: distance asc, id asc; IP: distance desc, id desc), padded with
+ * id -1 and the neutral distance.  With v the k-th best distance: a tie at v is eligible iff it is among the first k
+ * arrivals with distance <= v (>= v for IP); the result is the canonical top-k of {better than v} U {eligible ties} --
+ * HeapResultHandler's strict-improve admission with eviction by id, in closed form.  Exact whatever the row holds (the
+ * better entries and the ties are selected separately, each at most k).  Allocates 16 bytes x nq x the next power of two
+ * >= k of scratch for the call and drains the stream before it returns. */
+int knhip_select_ordered_device(int32_t metric, int64_t nq, int32_t k, const float* d_dist, int64_t row_stride,
+                                const int64_t* d_row_len, const int64_t* d_ids, float* d_out_dist, int64_t* d_out_ids,
+                                void* stream);
 
 /* ---- multi-GPU: merge of per-shard partial top-k ----
  * parts laid out [nshard][nq][k]; ids < 0 are empty slots. */

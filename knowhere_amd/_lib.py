@@ -63,6 +63,7 @@ SYMBOLS = [
     "knhip_fvec_L1_ny", "knhip_fvec_Linf_ny", "knhip_fvec_norms_L2sqr_ref", "knhip_fvec_L2sqr_ny_transposed",
     "knhip_fvec_L2sqr_ny_nearest", "knhip_fvec_L2sqr_ny_nearest_y_transposed", "knhip_fvec_madd_and_argmin",
     "knhip_fvec_batch_4", "knhip_typed_vec_ny", "knhip_typed_vec_batch_4", "knhip_ivec_ny",
+    "knhip_select_ordered_device",
     "knhip_iter_create", "knhip_iter_next", "knhip_iter_next_all", "knhip_iter_has_next", "knhip_iter_stats", "knhip_iter_destroy",
 ]
 
@@ -156,6 +157,7 @@ def load():
     L.knhip_refine_combine_device.argtypes = [i32, i64, vp, vp, vp]
     L.knhip_refine_select_device.argtypes = [i32, i64, vp, vp, i32, i32, vp, vp, vp]
     L.knhip_refine_select_host.argtypes = [i32, i64, vp, vp, i32, i32, vp, vp]
+    L.knhip_select_ordered_device.argtypes = [i32, i64, i32, vp, i64, vp, vp, vp, vp, vp]
     for f in ("knhip_fvec_L2sqr_ny", "knhip_fvec_inner_products_ny", "knhip_int8_vec_L2sqr_ny",
               "knhip_int8_vec_inner_products_ny"):
         getattr(L, f).argtypes = [vp, vp, vp, i64, i64, vp]

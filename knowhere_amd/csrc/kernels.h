@@ -159,6 +159,7 @@ struct PqScanArgs {
     float* dump;
     int64_t dump_stride;
     int32_t dump_by_row;           // 1: column = storage position of the vector (list_row_off + offset), range search
+    const int64_t* dump_pair_col;  // non-null (compact dump, large-k search): pair (q, slot) starts at dump[dump_pair_col[q * nslot + slot]]
     // per-query candidate histogram (pq_scan_v2 after a rank-0 phase; null = off): ghist[q][64] counts the
     // vectors seen so far per distance bin, gmeta[q] = {key of the first bin, bin shift | KN_HIST_OFF}
     uint32_t* ghist;
@@ -196,6 +197,7 @@ struct SqScanArgs {
     // range search: non-null = write every distance to dump[q * dump_stride + storage position], no top-k
     float* dump;
     int64_t dump_stride;
+    const int64_t* dump_pair_col; // non-null (compact dump, large-k search): pair (q, slot) starts at dump[dump_pair_col[q * nslot + slot]]
     int32_t item_loop;           // 1 = the (fixed) grid walks items blockIdx.x, + gridDim.x, ... < *nitems_dev
 };
 
@@ -487,6 +489,7 @@ hipError_t launch_tie_resolve(const int32_t* flagged, int nflag, int nsh, const 
 struct PqDumpArgs {
     float* dist;                 // [nq][ncol], column = list_row_off[list] + position
     int64_t ncol;
+    const int64_t* pair_col;     // non-null (compact dump): pair (q, slot) starts at dist[pair_col[q * nprobe + slot]]
     const int64_t* keys;         // [nq][nprobe] probed lists (coarse order)
     const float* coarse_dis;     // [nq][nprobe]
     int32_t nprobe;
@@ -545,7 +548,7 @@ hipError_t launch_range_wave_state(const int32_t* cnt, int64_t nq, int nprobe, i
                                    int32_t* qstate, int32_t* alive, hipStream_t s);
 hipError_t launch_range_flat_dump(const FlatScanArgs& a, const int64_t* keys_w, int64_t nq, int W, int64_t nlist,
                                   const int64_t* seg_col, const int64_t* seg_len, float* dist, int64_t ncol, bool is_l2,
-                                  hipStream_t s);
+                                  hipStream_t s, const int64_t* pair_col = nullptr);
 hipError_t launch_range_plan(const int32_t* cnt, int64_t nq, int nprobe, int max_empty, int64_t* off, int64_t* total,
                              hipStream_t s);
 hipError_t launch_range_emit(const RangeArgs& a, int64_t nq, bool is_l2, const int64_t* off, const int64_t* qbase,
@@ -570,6 +573,42 @@ hipError_t launch_row_select(const float* vals, int64_t nrows, int64_t n, int k,
                              int64_t* out_keys, float* out_d, const int32_t* row_flags, hipStream_t s,
                              unsigned long long* sort_scratch = nullptr);
 size_t row_select_lds_max_k();
+// ordered top-k of a row given in ARRIVAL order (topk.hip: the reference heap's answer at the k-th boundary, any k up to
+// ordered_topk_max_k()).  Row q = dist + (row_off ? row_off[q] : q * row_stride), its length seg_col[q][nseg] / row_len[q] /
+// n_fixed.  Column -> id: ids_dense (an array laid out like dist; negative = absent, stop_at_neg1: the first -1 ends the
+// row), or the segment map of a compact dump (seg_col [nq][nseg + 1] first column of each probe rank, seg_key [nq][nseg]
+// its list, seg_idpos [nlist] the list's first entry in ids[]), or column + id_offset (then `bitset` may filter, and
+// `reverse` walks the row backwards: the canonical answer of an inner-product row whose ids ascend).
+struct OrdSelArgs {
+    const float* dist;
+    int64_t row_stride;
+    const int64_t* row_off;
+    const int64_t* row_len;
+    int64_t n_fixed;
+    const int64_t* ids_dense;
+    int32_t stop_at_neg1;
+    const int64_t* seg_col;
+    const int64_t* seg_key;
+    const int64_t* seg_idpos;
+    const int64_t* ids;
+    int32_t nseg;
+    int64_t id_offset;
+    const uint8_t* bitset;
+    int64_t bitset_nbits;
+    int32_t reverse;
+    float* out_d;                 // [nq][k] heap_reorder order, padded with the neutral distance / id -1
+    int64_t* out_i;
+    int32_t k, kp;                // (kp: set by the launcher)
+    unsigned long long* scratch;  // ordered_topk_scratch_bytes(nq, k)
+};
+int ordered_topk_max_k();
+size_t ordered_topk_scratch_bytes(int64_t nq, int k);
+hipError_t launch_ordered_topk(const OrdSelArgs& a, int64_t nq, bool is_l2, hipStream_t s);
+// compact dump of the large-k path: filtered rows of (query, rank) -> the neutral distance (the flat and plain ADC dump
+// kernels write every row's distance)
+hipError_t launch_dump_mask(float* dump, const int64_t* pair_col, const int64_t* keys, int64_t nq, int nprobe, int64_t nlist,
+                            const int64_t* list_len, const int64_t* list_idpos, const int64_t* ids, const uint8_t* bitset,
+                            int64_t bitset_nbits, bool is_l2, hipStream_t s);
 // rows of different length: row r has n = list_len[keys[r * key_stride]] values at vals + r * stride
 hipError_t launch_row_select_var(const float* vals, int64_t stride, const int64_t* keys, int key_stride,
                                  const int64_t* list_len, int64_t nrows, int k, bool is_l2, int64_t* out_keys,

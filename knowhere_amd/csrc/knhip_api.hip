@@ -1537,8 +1537,8 @@ int validate_search(const knhip_index* idx, int64_t nq, int32_t k, int32_t& npro
     if (nq < 0 || k <= 0) {
         return fail(KNHIP_ERR_INVALID_ARGS, "nq must be >= 0 and k > 0");
     }
-    if (k > KN_MAX_K) {
-        return fail(KNHIP_ERR_INVALID_ARGS, "k > 1024 is not supported");
+    if (k > KNHIP_MAX_K) { // (1024 < k <= 16384: the large-k path, knhip_api_range.hip)
+        return fail(KNHIP_ERR_INVALID_ARGS, "k > 16384 is not supported");
     }
     const int kind = idx->desc.kind;
     if (kind == KNHIP_BRUTE_FORCE) {
@@ -2100,6 +2100,40 @@ struct RefineStore {
     const float* sq = nullptr;    // device: vmin[d], vdiff[d] (sq8)
 };
 
+// Refine with more than 1024 candidates per query: refine_kernel keeps four queries' candidate distances in LDS, which ends
+// there.  Above it the distances come from its distances-only mode (or are given), and the ordered top-k kernel (topk.hip)
+// applies reorder_2_heaps' rule -- candidate order is arrival order, the first -1 label ends the row, slots without a
+// distance are skipped -- at any k <= k_base <= KNHIP_MAX_K.  Scratch is allocated for the call and the stream is drained.
+static int refine_large(const float* base, int64_t nbase, int64_t id_base, int d, const float* d_q, int64_t nq,
+                        const int64_t* cand, int kbase, int k, bool is_l2, float* out_d, int64_t* out_i, hipStream_t s,
+                        int row_type, const float* sq, const float* dist_in) {
+    if (nq <= 0) {
+        return KNHIP_OK;
+    }
+    DevBuf dist, scratch;
+    const float* dd = dist_in;
+    if (dd == nullptr) {
+        HIP_TRY(dist.alloc((size_t)nq * kbase * sizeof(float)));
+        HIP_TRY(launch_refine(base, nbase, id_base, d, d_q, nq, cand, kbase, 1, is_l2, nullptr, nullptr, s, row_type, sq, nullptr,
+                              dist.as<float>()));
+        dd = dist.as<float>();
+    }
+    HIP_TRY(scratch.alloc(ordered_topk_scratch_bytes(nq, k)));
+    OrdSelArgs o{};
+    o.dist = dd;
+    o.row_stride = kbase;
+    o.n_fixed = kbase;
+    o.ids_dense = cand;
+    o.stop_at_neg1 = 1;
+    o.out_d = out_d;
+    o.out_i = out_i;
+    o.k = k;
+    o.scratch = scratch.as<unsigned long long>();
+    HIP_TRY(launch_ordered_topk(o, nq, is_l2, s));
+    HIP_TRY(hipStreamSynchronize(s)); // (the scratch goes with this frame)
+    return KNHIP_OK;
+}
+
 static int search_host_impl(const knhip_index* idx, const RefineStore* raw, const float* queries, int64_t nq, int32_t k,
                             int32_t k_base, int32_t nprobe, const uint8_t* bitset, int64_t bitset_nbits,
                             int64_t* out_ids, float* out_dist) {
@@ -2152,9 +2186,17 @@ static int search_host_impl(const knhip_index* idx, const RefineStore* raw, cons
             HIP_TRY(ws->h_ref_d.reserve((size_t)nq * k * sizeof(float)));
             HIP_TRY(ws->h_ref_i.reserve((size_t)nq * k * sizeof(int64_t)));
             StageTimer t(idx, s, KNHIP_STAGE_REFINE);
-            HIP_TRY(launch_refine(static_cast<const float*>(raw->rows), raw->n, raw->id0, idx->d,
-                                  ws->h_queries.as<float>(), nq, res_i, k_base, k, idx->is_l2, ws->h_ref_d.as<float>(),
-                                  ws->h_ref_i.as<int64_t>(), s, raw->row_type, raw->sq));
+            if (k_base > KN_MAX_K) {
+                if (int r = refine_large(static_cast<const float*>(raw->rows), raw->n, raw->id0, idx->d, ws->h_queries.as<float>(),
+                                         nq, res_i, k_base, k, idx->is_l2, ws->h_ref_d.as<float>(), ws->h_ref_i.as<int64_t>(), s,
+                                         raw->row_type, raw->sq, nullptr)) {
+                    return r;
+                }
+            } else {
+                HIP_TRY(launch_refine(static_cast<const float*>(raw->rows), raw->n, raw->id0, idx->d,
+                                      ws->h_queries.as<float>(), nq, res_i, k_base, k, idx->is_l2, ws->h_ref_d.as<float>(),
+                                      ws->h_ref_i.as<int64_t>(), s, raw->row_type, raw->sq));
+            }
             res_d = ws->h_ref_d.as<float>();
             res_i = ws->h_ref_i.as<int64_t>();
         }
@@ -2358,7 +2400,7 @@ int knhip_index_find_vectors(const knhip_index* idx, int64_t n, const int64_t* i
 int knhip_refine_distances_device(int32_t metric, int32_t dim, const float* d_base, int64_t nbase, int64_t id_base,
                                   const float* d_queries, int64_t nq, const int64_t* d_cand_ids, int32_t k_base,
                                   float* d_out_dist, void* stream) {
-    if (dim <= 0 || nbase < 0 || nq < 0 || k_base <= 0 || k_base > KN_MAX_K || (nbase > 0 && !d_base) || !d_queries ||
+    if (dim <= 0 || nbase < 0 || nq < 0 || k_base <= 0 || k_base > KNHIP_MAX_K || (nbase > 0 && !d_base) || !d_queries ||
         !d_cand_ids || !d_out_dist || (metric != KNHIP_L2 && metric != KNHIP_IP)) {
         return fail(KNHIP_ERR_INVALID_ARGS, "refine_distances: bad arguments");
     }
@@ -2370,7 +2412,7 @@ int knhip_refine_distances_device(int32_t metric, int32_t dim, const float* d_ba
 int knhip_refine_rows_distances_device(int32_t metric, const knhip_rows* rows, int64_t id_base, const float* d_queries,
                                        int64_t nq, const int64_t* d_cand_ids, int32_t k_base, float* d_out_dist,
                                        void* stream) {
-    if (!rows || !rows->trained || nq < 0 || k_base <= 0 || k_base > KN_MAX_K || !d_queries || !d_cand_ids || !d_out_dist ||
+    if (!rows || !rows->trained || nq < 0 || k_base <= 0 || k_base > KNHIP_MAX_K || !d_queries || !d_cand_ids || !d_out_dist ||
         (metric != KNHIP_L2 && metric != KNHIP_IP)) {
         return fail(KNHIP_ERR_INVALID_ARGS, "refine_rows_distances: bad arguments");
     }
@@ -2390,9 +2432,13 @@ int knhip_refine_combine_device(int32_t nshards, int64_t n, const float* d_parts
 
 int knhip_refine_select_device(int32_t metric, int64_t nq, const int64_t* d_cand_ids, const float* d_dist, int32_t k_base,
                                int32_t k, float* d_out_dist, int64_t* d_out_ids, void* stream) {
-    if (nq < 0 || k <= 0 || k > KN_MAX_K || k_base < k || !d_cand_ids || !d_dist || !d_out_dist || !d_out_ids ||
+    if (nq < 0 || k <= 0 || k_base > KNHIP_MAX_K || k_base < k || !d_cand_ids || !d_dist || !d_out_dist || !d_out_ids ||
         (metric != KNHIP_L2 && metric != KNHIP_IP)) {
         return fail(KNHIP_ERR_INVALID_ARGS, "refine_select: bad arguments");
+    }
+    if (k_base > KN_MAX_K) {
+        return refine_large(nullptr, 0, 0, 4, nullptr, nq, d_cand_ids, k_base, k, metric == KNHIP_L2, d_out_dist, d_out_ids,
+                            static_cast<hipStream_t>(stream), 0, nullptr, d_dist);
     }
     HIP_TRY(launch_refine(nullptr, 0, 0, 4, nullptr, nq, d_cand_ids, k_base, k, metric == KNHIP_L2, d_out_dist, d_out_ids,
                           static_cast<hipStream_t>(stream), 0, nullptr, d_dist, nullptr));
@@ -2491,6 +2537,33 @@ int knhip_coarse_search_device(const knhip_index* idx, const float* d_queries, i
     return KNHIP_OK;
 }
 
+int knhip_select_ordered_device(int32_t metric, int64_t nq, int32_t k, const float* d_dist, int64_t row_stride,
+                                const int64_t* d_row_len, const int64_t* d_ids, float* d_out_dist, int64_t* d_out_ids,
+                                void* stream) {
+    if (nq < 0 || k <= 0 || k > KNHIP_MAX_K || row_stride < 0 || row_stride > 0x7fffffffll || !d_dist || !d_row_len ||
+        !d_out_dist || !d_out_ids || (metric != KNHIP_L2 && metric != KNHIP_IP)) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "select_ordered: bad arguments");
+    }
+    if (nq == 0) {
+        return KNHIP_OK;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DevBuf scratch;
+    HIP_TRY(scratch.alloc(ordered_topk_scratch_bytes(nq, k)));
+    OrdSelArgs o{};
+    o.dist = d_dist;
+    o.row_stride = row_stride;
+    o.row_len = d_row_len;
+    o.ids_dense = d_ids;
+    o.out_d = d_out_dist;
+    o.out_i = d_out_ids;
+    o.k = k;
+    o.scratch = scratch.as<unsigned long long>();
+    HIP_TRY(launch_ordered_topk(o, nq, metric == KNHIP_L2, s));
+    HIP_TRY(hipStreamSynchronize(s)); // (the scratch goes with this frame)
+    return KNHIP_OK;
+}
+
 int knhip_merge_topk_device(int32_t metric, int64_t nq, int32_t k, int32_t nshard,
                             const float* d_dist_parts, const int64_t* d_ids_parts, float* d_out_dist,
                             int64_t* d_out_ids, void* stream) {
@@ -2547,9 +2620,13 @@ int knhip_merge_topk_host(int32_t metric, int64_t nq, int32_t k, int32_t nshard,
 int knhip_refine_device(int32_t metric, int32_t dim, const float* d_base, int64_t nbase, int64_t id_base,
                         const float* d_queries, int64_t nq, const int64_t* d_cand_ids, int32_t k_base,
                         int32_t k, float* d_out_dist, int64_t* d_out_ids, void* stream) {
-    if (dim <= 0 || nbase < 0 || nq < 0 || k <= 0 || k > KN_MAX_K || k_base < k || (nbase > 0 && !d_base) || !d_queries ||
+    if (dim <= 0 || nbase < 0 || nq < 0 || k <= 0 || k_base > KNHIP_MAX_K || k_base < k || (nbase > 0 && !d_base) || !d_queries ||
         !d_cand_ids || !d_out_dist || !d_out_ids || (metric != KNHIP_L2 && metric != KNHIP_IP)) {
         return fail(KNHIP_ERR_INVALID_ARGS, "refine: bad arguments");
+    }
+    if (k_base > KN_MAX_K) {
+        return refine_large(d_base, nbase, id_base, dim, d_queries, nq, d_cand_ids, k_base, k, metric == KNHIP_L2, d_out_dist,
+                            d_out_ids, static_cast<hipStream_t>(stream), 0, nullptr, nullptr);
     }
     HIP_TRY(launch_refine(d_base, nbase, id_base, dim, d_queries, nq, d_cand_ids, k_base, k, metric == KNHIP_L2,
                           d_out_dist, d_out_ids, static_cast<hipStream_t>(stream)));
@@ -2559,9 +2636,14 @@ int knhip_refine_device(int32_t metric, int32_t dim, const float* d_base, int64_
 int knhip_refine_rows_device(int32_t metric, const knhip_rows* rows, int64_t id_base, const float* d_queries, int64_t nq,
                              const int64_t* d_cand_ids, int32_t k_base, int32_t k, float* d_out_dist, int64_t* d_out_ids,
                              void* stream) {
-    if (!rows || !rows->trained || rows->n <= 0 || nq < 0 || k <= 0 || k > KN_MAX_K || k_base < k || !d_queries ||
+    if (!rows || !rows->trained || rows->n <= 0 || nq < 0 || k <= 0 || k_base > KNHIP_MAX_K || k_base < k || !d_queries ||
         !d_cand_ids || !d_out_dist || !d_out_ids || (metric != KNHIP_L2 && metric != KNHIP_IP)) {
         return fail(KNHIP_ERR_INVALID_ARGS, "refine_rows: bad arguments");
+    }
+    if (k_base > KN_MAX_K) {
+        return refine_large(static_cast<const float*>(rows->codes.p), rows->n, id_base, rows->d, d_queries, nq, d_cand_ids, k_base,
+                            k, metric == KNHIP_L2, d_out_dist, d_out_ids, static_cast<hipStream_t>(stream), rows->row_type,
+                            rows->ranged() ? rows->sq.as<float>() : nullptr, nullptr);
     }
     HIP_TRY(launch_refine(static_cast<const float*>(rows->codes.p), rows->n, id_base, rows->d, d_queries, nq, d_cand_ids, k_base,
                           k, metric == KNHIP_L2, d_out_dist, d_out_ids, static_cast<hipStream_t>(stream), rows->row_type,

@@ -18,13 +18,21 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
                        int64_t nseg, int64_t ncol, int64_t* h_lims /*nq + 1, relative*/, std::vector<int64_t>& out_i,
                        std::vector<float>& out_d, hipStream_t s, const float* d_radius_q = nullptr,
                        int nprobe_limit = 0, const int64_t* pre_keys = nullptr, const float* pre_cdis = nullptr,
-                       RangeArgs* dump_only_out = nullptr, std::vector<int32_t>* out_cnt = nullptr) {
+                       RangeArgs* dump_only_out = nullptr, std::vector<int32_t>* out_cnt = nullptr,
+                       const int64_t* pair_col = nullptr, int64_t compact_elems = 0) {
+    // pair_col != nullptr (the large-k search, IVF kinds): the COMPACT dump -- pair (q, rank) starts at dump[pair_col[q *
+    // nprobe + rank]], compact_elems floats in all (the padded rows of the probed lists only), gaps and filtered rows hold
+    // the neutral distance; the dense [nq][ncol] layout stays for every other caller
     const int kind = idx->desc.kind;
     const bool is_l2 = idx->is_l2;
     const int d = idx->d;
     const int nprobe = (nprobe_limit > 0 && kind != KNHIP_BRUTE_FORCE) ? std::min<int64_t>(nprobe_limit, nseg) : (int)nseg;
     const bool all_lists = nprobe == (int)nseg;
-    HIP_TRY(ws->dump.reserve((size_t)nq * ncol * sizeof(float)));
+    const bool compact = pair_col != nullptr;
+    HIP_TRY(ws->dump.reserve((compact ? (size_t)std::max<int64_t>(compact_elems, 1) : (size_t)nq * ncol) * sizeof(float)));
+    if (compact) {
+        HIP_TRY(launch_fill_f32(ws->dump.as<float>(), compact_elems, is_l2 ? FLT_MAX : -FLT_MAX, s));
+    }
     RangeArgs r{};
     r.dist = ws->dump.as<float>();
     r.ncol = ncol;
@@ -70,12 +78,12 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
     // every distance of the lists keys_w[q][0 .. W) (-1: none) -> dump[q][column]
     auto scan_dump = [&](const int64_t* keys_w, const float* cdis_w, int W) -> int {
         if (kind == KNHIP_IVF_FLAT) {
-            if (W == nprobe && all_lists) {
+            if (W == nprobe && all_lists && !compact) {
                 // all lists of every query: the dense all-pairs kernel (rows shared by eight queries)
                 HIP_TRY(launch_flat_full(fc, is_l2, ws->dump.as<float>(), nullptr, 0, nullptr, s));
             } else {
                 HIP_TRY(launch_range_flat_dump(fc, keys_w, nq, W, idx->nlist, r.seg_col, r.seg_len, ws->dump.as<float>(),
-                                               ncol, is_l2, s));
+                                               ncol, is_l2, s, pair_col));
             }
             return KNHIP_OK;
         }
@@ -88,6 +96,7 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
             PqDumpArgs a{};
             a.dist = ws->dump.as<float>();
             a.ncol = ncol;
+            a.pair_col = pair_col;
             a.keys = keys_w;
             a.coarse_dis = cdis_w;
             a.nprobe = W;
@@ -161,6 +170,7 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
             a.dump = ws->dump.as<float>();
             a.dump_stride = ncol;
             a.dump_by_row = 1;
+            a.dump_pair_col = pair_col;
             HIP_TRY(launch_pq_scan_v2(a, is_l2, true, items_bound, s));
         } else {
             SqScanArgs a{};
@@ -186,6 +196,7 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
             a.k = 1;
             a.dump = ws->dump.as<float>();
             a.dump_stride = ncol;
+            a.dump_pair_col = pair_col;
             HIP_TRY(launch_sq_scan(a, is_l2, items_bound, s));
         }
         return KNHIP_OK;
@@ -237,6 +248,12 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
             idx->last_range_ranks = r0;
             counted = true;
         }
+    }
+    if (compact && d_bitset != nullptr &&
+        (kind == KNHIP_IVF_FLAT || (kind == KNHIP_IVF_PQ && !(idx->pq_v2 && idx->desc.pq_m == 32)))) {
+        // (these two dump kernels write every row's distance: the filtered ones become the neutral value here)
+        HIP_TRY(launch_dump_mask(ws->dump.as<float>(), pair_col, ws->keys.as<int64_t>(), nq, nprobe, idx->nlist, r.seg_len,
+                                 r.seg_idpos, idx->ids.as<int64_t>(), d_bitset, nbits, is_l2, s));
     }
     if (dump_only_out != nullptr) { // (the caller walks the dump itself: search_batch_ties)
         *dump_only_out = r;
@@ -455,10 +472,180 @@ static int read_word_now(Workspace* ws, const int32_t* d_word, int32_t* out, hip
 } // extern "C"
 
 namespace knhip_host {
+// ---- Search() with 1024 < k <= KNHIP_MAX_K -----------------------------------------------------------------------------------
+// The partial-top-k pipeline keeps nprobe x k x 12 bytes per query and a list is usually shorter than k, so a large k takes
+// another road: the coarse stage as ever (or the given assignment), then every exact distance of the probed lists in SCAN
+// order (probe rank, storage position) through the dump-mode kernels of the range search into a COMPACT row per query --
+// its probed lists only, each padded to 64 columns --, then one ordered top-k per row (topk.hip::ordered_topk_kernel: the
+// reference heap's answer, boundary ties included, at any k).  The queries go in rounds whose rows fill the dump up to
+// KNHIP_LARGEK_ROUND_KB (2 GiB); the host reads the batch's coarse keys once to lay the rows out.
+// BRUTE_FORCE: the full distance matrix of a round of queries + the same kernel over rows walked in canonical id order
+// (ascending for L2, descending for IP), which makes its answer the canonical one.
+static int search_batch_large_k(const knhip_index* idx, Workspace* ws, const float* d_q, int64_t nq, int k, int nprobe,
+                                const uint8_t* d_bitset, int64_t nbits, int64_t* d_out_i, float* d_out_d, hipStream_t s,
+                                const int64_t* pre_keys, const float* pre_cdis) {
+    const int kind = idx->desc.kind;
+    const bool is_l2 = idx->is_l2;
+    if (k > ordered_topk_max_k()) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "k > 16384 is not supported");
+    }
+    int64_t nseg = 0, ncol = 0;
+    const int64_t* d_seg = nullptr;
+    if (int rc = range_segments(idx, s, &d_seg, &nseg, &ncol)) return rc;
+    const size_t budget = env_search().largek_round_bytes;
+    std::vector<int64_t> lims_unused, hi_unused;
+    std::vector<float> hd_unused;
+    OrdSelArgs o{};
+    o.k = k;
+    if (kind == KNHIP_BRUTE_FORCE) {
+        const int64_t qb = std::max<int64_t>(1, (int64_t)(budget / ((size_t)std::max<int64_t>(ncol, 1) * 4)));
+        HIP_TRY(ws->lk_scratch.reserve(ordered_topk_scratch_bytes(std::min(qb, nq), k)));
+        for (int64_t q0 = 0; q0 < nq; q0 += qb) {
+            const int64_t n = std::min(qb, nq - q0);
+            lims_unused.assign((size_t)n + 1, 0);
+            RangeArgs r{};
+            {
+                StageTimer t(idx, s, KNHIP_STAGE_SCAN);
+                if (int rc = range_batch(idx, ws, d_q + q0 * idx->d, n, 0.f, 0, nullptr, 0, d_seg, nseg, ncol, lims_unused.data(),
+                                         hi_unused, hd_unused, s, nullptr, 0, nullptr, nullptr, &r)) {
+                    return rc;
+                }
+            }
+            StageTimer t(idx, s, KNHIP_STAGE_MERGE);
+            o.dist = r.dist;
+            o.row_stride = ncol;
+            o.n_fixed = ncol;
+            o.id_offset = idx->id_offset;
+            o.bitset = d_bitset;
+            o.bitset_nbits = nbits;
+            o.reverse = is_l2 ? 0 : 1;
+            o.out_d = d_out_d + q0 * k;
+            o.out_i = d_out_i + q0 * k;
+            o.scratch = ws->lk_scratch.as<unsigned long long>();
+            HIP_TRY(launch_ordered_topk(o, n, is_l2, s));
+        }
+        return KNHIP_OK;
+    }
+    // ---- the batch's coarse assignment, kept beside ws->keys (range_batch copies a round's slice there) ----
+    const size_t np = (size_t)nprobe;
+    HIP_TRY(ws->tie_keys.reserve((size_t)nq * np * sizeof(int64_t)));
+    HIP_TRY(ws->tie_cdis.reserve((size_t)nq * np * sizeof(float)));
+    if (pre_keys != nullptr) {
+        HIP_TRY(hipMemcpyAsync(ws->tie_keys.p, pre_keys, (size_t)nq * np * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ws->tie_cdis.p, pre_cdis, (size_t)nq * np * sizeof(float), hipMemcpyDeviceToDevice, s));
+    } else if (!is_l2 && nprobe < idx->nlist && nprobe <= ordered_topk_max_k()) {
+        // Inner product: the coarse quantizer's heap admits first-come too, and among centroids tied at the nprobe-th
+        // distance it keeps the EARLIEST, where the canonical order the coarse stage returns keeps the largest ids (for L2
+        // the two agree: ids arrive ascending).  Which lists are probed decides thousands of results here, so this path
+        // takes the reference's choice: every exact centroid distance, then the ordered top-nprobe over the centroid order.
+        FlatScanArgs c{};
+        c.rows = idx->centroids_il.as<float4>();
+        c.nrows = idx->nlist;
+        c.chunk_rows = 1024;
+        c.d = idx->d;
+        c.nchunk = (idx->d + 3) / 4;
+        c.queries = d_q;
+        c.nq = nq;
+        StageTimer t(idx, s, KNHIP_STAGE_COARSE);
+        HIP_TRY(ws->coarse_full.reserve((size_t)nq * idx->nlist * sizeof(float)));
+        HIP_TRY(launch_flat_full(c, false, ws->coarse_full.as<float>(), nullptr, 0, nullptr, s));
+        HIP_TRY(ws->lk_scratch.reserve(ordered_topk_scratch_bytes(nq, nprobe)));
+        OrdSelArgs oc{};
+        oc.dist = ws->coarse_full.as<float>();
+        oc.row_stride = idx->nlist;
+        oc.n_fixed = idx->nlist;
+        oc.out_d = ws->tie_cdis.as<float>();
+        oc.out_i = ws->tie_keys.as<int64_t>();
+        oc.k = nprobe;
+        oc.scratch = ws->lk_scratch.as<unsigned long long>();
+        HIP_TRY(launch_ordered_topk(oc, nq, false, s));
+    } else {
+        HIP_TRY(ws->keys.reserve((size_t)nq * np * sizeof(int64_t)));
+        HIP_TRY(ws->cdis.reserve((size_t)nq * np * sizeof(float)));
+        StageTimer t(idx, s, KNHIP_STAGE_COARSE);
+        if (int rc = coarse_stage(idx, ws, d_q, nq, nprobe, ws->tie_keys.as<int64_t>(), ws->tie_cdis.as<float>(), s)) return rc;
+    }
+    std::vector<int64_t> h_keys((size_t)nq * np);
+    HIP_TRY(hipMemcpyAsync(h_keys.data(), ws->tie_keys.p, h_keys.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    // plan [seg_col: nq x (np + 1) | row_off: nq | pair_col: nq x np]; rounds = runs of queries whose rows fit the budget
+    std::vector<int64_t> plan((size_t)nq * (2 * np + 2));
+    int64_t* seg_col = plan.data();
+    int64_t* row_off = seg_col + (size_t)nq * (np + 1);
+    int64_t* pcol = row_off + nq;
+    std::vector<int64_t> round_q0, round_elems;
+    int64_t run = 0;
+    for (int64_t q = 0; q < nq; q++) {
+        int64_t col = 0;
+        for (size_t r = 0; r < np; r++) {
+            const int64_t key = h_keys[(size_t)q * np + r];
+            seg_col[(size_t)q * (np + 1) + r] = col;
+            col += (key >= 0 && key < idx->nlist) ? round_up(idx->h_list_len[key], 64) : 0;
+        }
+        seg_col[(size_t)q * (np + 1) + np] = col;
+        if (col > 0x7fffffffll) {
+            return fail(KNHIP_ERR_NOT_IMPLEMENTED, "large-k search: more than 2^31 probed rows per query");
+        }
+        if (round_q0.empty() || (run > 0 && (size_t)(run + col) * 4 > budget)) {
+            round_q0.push_back(q);
+            round_elems.push_back(0);
+            run = 0;
+        }
+        row_off[q] = run;
+        for (size_t r = 0; r < np; r++) {
+            pcol[(size_t)q * np + r] = run + seg_col[(size_t)q * (np + 1) + r];
+        }
+        run += col;
+        round_elems.back() = run;
+    }
+    HIP_TRY(ws->lk_plan.reserve(plan.size() * sizeof(int64_t)));
+    HIP_TRY(hipMemcpyAsync(ws->lk_plan.p, plan.data(), plan.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s)); // (the host vector is released on return)
+    const int64_t* d_seg_col = ws->lk_plan.as<int64_t>();
+    const int64_t* d_row_off = d_seg_col + (size_t)nq * (np + 1);
+    const int64_t* d_pcol = d_row_off + nq;
+    int64_t max_n = 0;
+    for (size_t i = 0; i < round_q0.size(); i++) {
+        max_n = std::max(max_n, (i + 1 < round_q0.size() ? round_q0[i + 1] : nq) - round_q0[i]);
+    }
+    HIP_TRY(ws->lk_scratch.reserve(ordered_topk_scratch_bytes(max_n, k)));
+    for (size_t i = 0; i < round_q0.size(); i++) {
+        const int64_t q0 = round_q0[i];
+        const int64_t n = (i + 1 < round_q0.size() ? round_q0[i + 1] : nq) - q0;
+        lims_unused.assign((size_t)n + 1, 0);
+        RangeArgs r{};
+        {
+            StageTimer t(idx, s, KNHIP_STAGE_SCAN);
+            if (int rc = range_batch(idx, ws, d_q + q0 * idx->d, n, 0.f, 0, d_bitset, nbits, d_seg, nseg, ncol, lims_unused.data(),
+                                     hi_unused, hd_unused, s, nullptr, nprobe, ws->tie_keys.as<int64_t>() + (size_t)q0 * np,
+                                     ws->tie_cdis.as<float>() + (size_t)q0 * np, &r, nullptr, d_pcol + (size_t)q0 * np,
+                                     round_elems[i])) {
+                return rc;
+            }
+        }
+        StageTimer t(idx, s, KNHIP_STAGE_MERGE);
+        o.dist = r.dist;
+        o.row_off = d_row_off + q0;
+        o.seg_col = d_seg_col + (size_t)q0 * (np + 1);
+        o.seg_key = ws->keys.as<int64_t>(); // (the round's slice, as range_batch left it)
+        o.seg_idpos = r.seg_idpos;
+        o.ids = r.ids;
+        o.nseg = nprobe;
+        o.out_d = d_out_d + q0 * k;
+        o.out_i = d_out_i + q0 * k;
+        o.scratch = ws->lk_scratch.as<unsigned long long>();
+        HIP_TRY(launch_ordered_topk(o, n, is_l2, s));
+    }
+    return KNHIP_OK;
+}
+
 int search_batch_ties(const knhip_index* idx, Workspace* ws, const float* d_q, int64_t nq, int k, int nprobe,
                              const uint8_t* d_bitset, int64_t nbits, int64_t* d_out_i, float* d_out_d, hipStream_t s,
                              const int64_t* pre_keys, const float* pre_cdis) {
     const int kind = idx->desc.kind;
+    if (k > KN_MAX_K) {
+        return search_batch_large_k(idx, ws, d_q, nq, k, nprobe, d_bitset, nbits, d_out_i, d_out_d, s, pre_keys, pre_cdis);
+    }
     if (!knhip_ties_rule_applies(kind, k)) {
         return search_batch(idx, ws, d_q, nq, k, nprobe, d_bitset, nbits, d_out_i, d_out_d, s, pre_keys, pre_cdis);
     }
@@ -519,6 +706,9 @@ int knhip_search_canonical_device(const knhip_index* idx, const float* d_queries
                                   int64_t bitset_nbits, int64_t* d_out_ids, float* d_out_dist, void* stream) {
     if (int rc = check_index(idx)) return rc;
     const int32_t nprobe_in = nprobe;
+    if (k > KN_MAX_K) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "search_canonical: k > 1024 is not supported (the large-k path is one index's own)");
+    }
     if (int rc = validate_search(idx, nq, k, nprobe)) return rc;
     const bool pre = d_keys != nullptr || d_coarse_dis != nullptr;
     if (pre && (idx->desc.kind == KNHIP_BRUTE_FORCE || !d_keys || !d_coarse_dis || nprobe != nprobe_in)) {

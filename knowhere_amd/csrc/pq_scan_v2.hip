@@ -364,8 +364,10 @@ __device__ __forceinline__ void p2_process_item(const PqScanArgs& a, unsigned ch
                         for (int qi = 0; qi < QG; qi++) {
                             if (qi < npair) {
                                 const float o = qi == 0 ? Y.x : Y.y;
-                                a.dump[(int64_t)q_of[qi] * a.dump_stride + (a.dump_by_row ? row_off : 0) + vbase + lane] =
-                                        filt ? worst_dist<IS_L2>() : fadd_x(dis0[qi], o);
+                                const int64_t at = a.dump_pair_col != nullptr
+                                                           ? a.dump_pair_col[(int64_t)q_of[qi] * a.nslot + slot_of[qi]]
+                                                           : (int64_t)q_of[qi] * a.dump_stride + (a.dump_by_row ? row_off : 0);
+                                a.dump[at + vbase + lane] = filt ? worst_dist<IS_L2>() : fadd_x(dis0[qi], o);
                             }
                         }
                     }

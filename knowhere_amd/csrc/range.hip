@@ -133,7 +133,8 @@ __global__ __launch_bounds__(RG_THREADS) void range_flat_dump_kernel(FlatScanArg
                                                                      int W, int64_t nlist,
                                                                      const int64_t* __restrict__ seg_col,
                                                                      const int64_t* __restrict__ seg_len,
-                                                                     float* __restrict__ dist, int64_t ncol) {
+                                                                     float* __restrict__ dist, int64_t ncol,
+                                                                     const int64_t* __restrict__ pair_col) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int64_t q = blockIdx.x / W;
     const int64_t key = keys_w[blockIdx.x];
@@ -145,6 +146,8 @@ __global__ __launch_bounds__(RG_THREADS) void range_flat_dump_kernel(FlatScanArg
         return;
     }
     const int64_t col0 = seg_col[key]; // (a multiple of 64: lists start on a block)
+    // (compact dump of the large-k search: the pair's own first element instead of the list's column in the query's row)
+    float* out = pair_col != nullptr ? dist + pair_col[blockIdx.x] : dist + q * ncol + col0;
     const int dpad = a.nchunk * 4;
     float* sq = reinterpret_cast<float*>(smem);
     for (int i = threadIdx.x; i < dpad; i += RG_THREADS) {
@@ -178,7 +181,7 @@ __global__ __launch_bounds__(RG_THREADS) void range_flat_dump_kernel(FlatScanArg
             if (!IS_L2 && a.cos_mode != 0) {
                 acc = cosine_finish(acc, a.row_scale[col0 + row], a.cos_mode);
             }
-            dist[q * ncol + col0 + row] = acc;
+            out[row] = acc;
         }
     }
 }
@@ -310,7 +313,7 @@ __global__ __launch_bounds__(RG_THREADS) void pq_adc_dump_kernel(PqDumpArgs a) {
     __syncthreads();
     const float dis0 = a.lut_mode == PQ_LUT_RESIDUAL ? 0.f : a.coarse_dis[q * a.nprobe + slot];
     const int64_t row_off = a.list_row_off[list];
-    float* out = a.dist + q * a.ncol + row_off;
+    float* out = a.pair_col != nullptr ? a.dist + a.pair_col[blockIdx.x] : a.dist + q * a.ncol + row_off;
     for (int64_t pos = threadIdx.x; pos < len; pos += RG_THREADS) {
         const uint8_t* code = a.codes + (row_off + pos) * M;
         float acc = 0.f;
@@ -386,7 +389,7 @@ hipError_t launch_range_wave_state(const int32_t* cnt, int64_t nq, int nprobe, i
 
 hipError_t launch_range_flat_dump(const FlatScanArgs& a, const int64_t* keys_w, int64_t nq, int W, int64_t nlist,
                                   const int64_t* seg_col, const int64_t* seg_len, float* dist, int64_t ncol, bool is_l2,
-                                  hipStream_t s) {
+                                  hipStream_t s, const int64_t* pair_col) {
     if (nq <= 0 || W <= 0) {
         return hipSuccess;
     }
@@ -400,7 +403,41 @@ hipError_t launch_range_flat_dump(const FlatScanArgs& a, const int64_t* keys_w, 
         }
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)(nq * W)), dim3(RG_THREADS), sm, s, a, keys_w, W, nlist, seg_col, seg_len,
-                       dist, ncol);
+                       dist, ncol, pair_col);
+    return hipGetLastError();
+}
+
+// ---- compact dump of the large-k search: the flat and plain ADC dumps write every row's distance; the rows the bitset
+// filters become the neutral distance, as the SQ and stream16 dumps write them (one workgroup per (query, rank)) ---------
+template <bool IS_L2>
+__global__ __launch_bounds__(RG_THREADS) void dump_mask_kernel(float* __restrict__ dump, const int64_t* __restrict__ pair_col,
+                                                               const int64_t* __restrict__ keys, int64_t nlist,
+                                                               const int64_t* __restrict__ list_len,
+                                                               const int64_t* __restrict__ list_idpos,
+                                                               const int64_t* __restrict__ ids,
+                                                               const uint8_t* __restrict__ bitset, int64_t bitset_nbits) {
+    const int64_t key = keys[blockIdx.x];
+    if (key < 0 || key >= nlist) {
+        return;
+    }
+    const int64_t len = list_len[key], idp = list_idpos[key];
+    float* out = dump + pair_col[blockIdx.x];
+    for (int64_t i = threadIdx.x; i < len; i += RG_THREADS) {
+        if (bitset_filtered(bitset, bitset_nbits, ids[idp + i])) {
+            out[i] = worst_dist<IS_L2>();
+        }
+    }
+}
+
+hipError_t launch_dump_mask(float* dump, const int64_t* pair_col, const int64_t* keys, int64_t nq, int nprobe, int64_t nlist,
+                            const int64_t* list_len, const int64_t* list_idpos, const int64_t* ids, const uint8_t* bitset,
+                            int64_t bitset_nbits, bool is_l2, hipStream_t s) {
+    if (nq <= 0 || nprobe <= 0 || bitset == nullptr) {
+        return hipSuccess;
+    }
+    auto kern = is_l2 ? dump_mask_kernel<true> : dump_mask_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nq * nprobe)), dim3(RG_THREADS), 0, s, dump, pair_col, keys, nlist, list_len,
+                       list_idpos, ids, bitset, bitset_nbits);
     return hipGetLastError();
 }
 

@@ -93,7 +93,9 @@ __global__ __launch_bounds__(256) void refine_kernel(const float* __restrict__ b
     const int64_t q = (int64_t)blockIdx.x * 4 + wave;
     const bool live = q < nq;
     float* myq = sq + wave * d;
-    float* mydis = sq + 4 * d + wave * kbase;
+    // (distances-only mode keeps no candidate distances in LDS: k_base may exceed what four rows of them would take)
+    const int kb_lds = dist_out != nullptr ? 0 : kbase;
+    float* mydis = sq + 4 * d + wave * kb_lds;
     if (live && dist_in == nullptr) {
         for (int i = lane; i < d; i += KN_WAVE) {
             myq[i] = queries[q * d + i];
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(256) void refine_kernel(const float* __restrict__ b
             const float4* b4 = reinterpret_cast<const float4*>(base);
             const float4* q4 = reinterpret_cast<const float4*>(myq);
             const int n4 = d >> 2;
-            unsigned char* st = reinterpret_cast<unsigned char*>(sq + 4 * d + 4 * kbase) + wave * (KN_WAVE * RF_PITCH);
+            unsigned char* st = reinterpret_cast<unsigned char*>(sq + 4 * d + 4 * kb_lds) + wave * (KN_WAVE * RF_PITCH);
             const int sub = lane >> 4, pl = lane & 15;
             for (int p0 = 0; p0 < n4; p0 += 16) { // 16 pieces = 64 dimensions of every row
                 float4 v[16];
@@ -261,7 +263,7 @@ __global__ __launch_bounds__(256) void refine_kernel(const float* __restrict__ b
                 acc = IS_L2 ? l2_step(acc, myq[i], y[i]) : ip_step(acc, myq[i], y[i]);
             }
         }
-        if (c < kbase) {
+        if (c < kbase && dist_out == nullptr) {
             mydis[c] = acc;
         }
         if (dist_out != nullptr) {
@@ -349,7 +351,7 @@ hipError_t launch_refine(const float* base, int64_t nbase, int64_t id_base, int 
     // a base pointer may legitimately be null then.  ADVICE round 5)
     int coop = (row_type == 0 && dist_in == nullptr && nbase > 0 && base != nullptr && (d & 3) == 0 &&
                 (reinterpret_cast<uintptr_t>(base) & 15) == 0) ? 1 : 0;
-    const size_t sm_plain = ((size_t)4 * d + (size_t)4 * kbase) * sizeof(float);
+    const size_t sm_plain = ((size_t)4 * d + (dist_out != nullptr ? 0 : (size_t)4 * kbase)) * sizeof(float);
     size_t sm = sm_plain + (coop ? (size_t)4 * KN_WAVE * RF_PITCH : 0);
     if (sm > 160 * 1024 && coop) {
         // the staging area (69.6 KB) does not fit beside four long queries: the lane-per-row gather still does

@@ -161,7 +161,10 @@ __device__ __forceinline__ void sq_scan_item(const SqScanArgs& a, const int64_t 
                 // range search: every distance of the list, filtered rows as the sentinel
                 if (row < len) {
                     const float dis = IS_L2 ? acc[j] : fadd_x(accu0[j], acc[j]);
-                    a.dump[(int64_t)q_of[j] * a.dump_stride + row_off + row] = valid ? dis : worst_dist<IS_L2>();
+                    const int64_t at = a.dump_pair_col != nullptr
+                                               ? a.dump_pair_col[(int64_t)q_of[j] * a.nslot + slot_of[j]]
+                                               : (int64_t)q_of[j] * a.dump_stride + row_off;
+                    a.dump[at + row] = valid ? dis : worst_dist<IS_L2>();
                 }
             } else if (j < npair) {
                 const float dis = IS_L2 ? acc[j] : fadd_x(accu0[j], acc[j]);

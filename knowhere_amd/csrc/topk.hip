@@ -774,4 +774,379 @@ hipError_t launch_row_select_var(const float* vals, int64_t stride, const int64_
     return hipGetLastError();
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// ordered_topk: the reference heap's k results of a row of distances given in ARRIVAL order, for any k up to
+// OT_MAX_K (the large-k path of Search() and refine; include/knhip.h knhip_select_ordered_device).
+//
+// HeapResultHandler admits a candidate only if it beats the current k-th and evicts, among equal distances, the
+// canonically worst id (see knhip_api_range.hip).  With v the k-th best distance of the row that is the closed form
+//     a tie at v is ELIGIBLE iff it is among the first k arrivals with distance <= v (L2; >= v for IP);
+//     result = canonical top-k of {better than v} U {eligible ties}
+// (tests/test_tie_rule.py replays the heap against it).  Every better entry sorts in front of every tie, so the result is
+// the b < k better entries in canonical order followed by the k - b canonically best of the (at most k) eligible ties:
+// two selections of at most k entries each, never one of 2 k - 1 -- each fits the LDS at k = 16384 as 8-byte entries.
+//
+// One 1024-thread workgroup per row, LDS = 8 bytes x next power of two >= k (128 KB at most):
+//   1. radix select of v over order-preserving keys (4 x 8-bit digits); distance rows pile into a few bins, so a wave
+//      first peels up to three shared digits with one atomic each and only the rest adds lane by lane
+//   2. ordered walk, ballot prefix counts: the ties among the first k arrivals with key <= v -> their ids into LDS,
+//      sorted, the first k - b written behind the better block
+//   3. the better entries (key, column) -> LDS; canonical order needs (distance, id) and an id is 64 bits, so the ids
+//      are sorted first (LDS), each entry takes the RANK of its id (binary search) and (key, rank) is sorted --
+//      entries and sorted ids pass through 2 x kp x 8 bytes of global scratch per row while the LDS changes hands
+// An entry is absent when its distance is not better than the neutral value (+-FLT_MAX, NaN: what the dump kernels
+// write for filtered rows and padding, what the heap itself never admits), when its id is negative, or when the
+// bitset filters it.
+// ---------------------------------------------------------------------------------------------
+constexpr int OT_THREADS = 1024;
+constexpr int OT_WAVES = OT_THREADS / KN_WAVE;
+constexpr int OT_MAX_K = 16384;
+constexpr uint32_t OT_ABSENT = 0xffffffffu;
+constexpr unsigned long long OT_SIGN = 0x8000000000000000ull;
+
+template <bool IS_L2>
+__device__ __forceinline__ unsigned long long ot_idkey(int64_t id) { // ascending = canonical id order
+    const unsigned long long u = (unsigned long long)id ^ OT_SIGN;
+    return IS_L2 ? u : ~u;
+}
+template <bool IS_L2>
+__device__ __forceinline__ int64_t ot_unidkey(unsigned long long kk) {
+    return (int64_t)((IS_L2 ? kk : ~kk) ^ OT_SIGN);
+}
+
+// id of column `col` of row q
+__device__ __forceinline__ int64_t ot_id_of(const OrdSelArgs& a, int64_t q, int64_t rowbase, int64_t col) {
+    if (a.ids_dense != nullptr) {
+        return a.ids_dense[rowbase + col];
+    }
+    if (a.seg_col != nullptr) {
+        const int64_t* sc = a.seg_col + q * (a.nseg + 1);
+        int lo = 0, hi = a.nseg; // last rank whose first column is <= col
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (sc[mid] <= col) {
+                lo = mid;
+            } else {
+                hi = mid;
+            }
+        }
+        const int64_t key = a.seg_key[q * a.nseg + lo];
+        const int64_t pos = a.seg_idpos[key] + (col - sc[lo]);
+        return a.ids != nullptr ? a.ids[pos] : pos + a.id_offset;
+    }
+    return col + a.id_offset;
+}
+
+template <bool IS_L2>
+__device__ __forceinline__ uint32_t ot_key(const OrdSelArgs& a, const float* row, int64_t rowbase, int64_t col) {
+    const float d = row[col];
+    bool valid = IS_L2 ? (d < FLT_MAX) : (d > -FLT_MAX);
+    if (a.ids_dense != nullptr) {
+        valid = valid && a.ids_dense[rowbase + col] >= 0;
+    } else if (a.bitset != nullptr && valid) {
+        valid = !bitset_filtered(a.bitset, a.bitset_nbits, col + a.id_offset);
+    }
+    return valid ? rs_key<IS_L2>(d) : OT_ABSENT;
+}
+
+// bitonic sort of c[0 .. m), m a power of two (ends on a barrier)
+__device__ __forceinline__ void ot_sort(unsigned long long* c, int m) {
+    for (int size = 2; size <= m; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < m / 2; t += OT_THREADS) {
+                const int lo = (t / stride) * stride * 2 + (t % stride);
+                const int hi = lo + stride;
+                const bool up = ((lo & size) == 0);
+                const unsigned long long x = c[lo], y = c[hi];
+                if ((x > y) == up) {
+                    c[lo] = y;
+                    c[hi] = x;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__device__ __forceinline__ int ot_pow2(int n) {
+    int m = 2;
+    while (m < n) {
+        m <<= 1;
+    }
+    return m;
+}
+
+template <bool IS_L2>
+__global__ __launch_bounds__(OT_THREADS) void ordered_topk_kernel(OrdSelArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    unsigned long long* cand = reinterpret_cast<unsigned long long*>(smem); // [kp]
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t s_wave[OT_WAVES];
+    __shared__ uint32_t s_prefix, s_need, s_count;
+    __shared__ unsigned long long s_end;
+    const int tid = threadIdx.x, lane = tid & (KN_WAVE - 1), wave = tid / KN_WAVE;
+    const int64_t q = blockIdx.x;
+    const int k = a.k;
+    const int64_t rowbase = a.row_off != nullptr ? a.row_off[q] : q * a.row_stride;
+    const float* row = a.dist + rowbase;
+    float* od = a.out_d + q * k;
+    int64_t* oi = a.out_i + q * k;
+    unsigned long long* S0 = a.scratch + q * 2 * (int64_t)a.kp;
+    unsigned long long* S1 = S0 + a.kp;
+    int64_t n = a.seg_col != nullptr ? a.seg_col[q * (a.nseg + 1) + a.nseg] : (a.row_len != nullptr ? a.row_len[q] : a.n_fixed);
+    if (a.ids_dense != nullptr && a.stop_at_neg1) { // the row ends in front of the first -1 label
+        if (tid == 0) {
+            s_end = (unsigned long long)n;
+        }
+        __syncthreads();
+        for (int64_t i = tid; i < n; i += OT_THREADS) {
+            if (a.ids_dense[rowbase + i] == -1) {
+                atomicMin(&s_end, (unsigned long long)i);
+                break;
+            }
+        }
+        __syncthreads();
+        n = (int64_t)s_end;
+    }
+    // arrival i of the row is column col(i): the row itself, or the row walked backwards
+    auto col_of = [&](int64_t i) -> int64_t { return a.reverse ? n - 1 - i : i; };
+    const int keff = (int)min((int64_t)k, n);
+    uint32_t T = OT_ABSENT, need = 0;
+    if (keff > 0) {
+        // ---- 1. radix select: T with count(key < T) < keff <= count(key <= T); absent entries sort last ----
+        uint32_t prefix = 0, prefix_mask = 0;
+        need = (uint32_t)keff;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) {
+                hist[tid] = 0;
+            }
+            __syncthreads();
+            for (int64_t i0 = 0; i0 < n; i0 += OT_THREADS) {
+                const int64_t i = i0 + tid;
+                uint32_t key = 0;
+                bool act = i < n;
+                if (act) {
+                    key = ot_key<IS_L2>(a, row, rowbase, i);
+                    act = (key & prefix_mask) == prefix;
+                }
+                const uint32_t dg = (key >> shift) & 0xffu;
+                unsigned long long rem = __ballot(act);
+                for (int it = 0; it < 3 && rem != 0ull; it++) {
+                    const int l = __ffsll((long long)rem) - 1;
+                    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)dg, l);
+                    const unsigned long long m = __ballot(act && dg == d0) & rem;
+                    if (lane == l) {
+                        atomicAdd(&hist[d0], (uint32_t)__popcll(m));
+                    }
+                    rem &= ~m;
+                }
+                if ((rem >> lane) & 1ull) {
+                    atomicAdd(&hist[dg], 1u);
+                }
+            }
+            __syncthreads();
+            uint32_t h = 0, c = 0;
+            if (tid < 256) {
+                h = hist[tid];
+                c = h;
+#pragma unroll
+                for (int dlt = 1; dlt < KN_WAVE; dlt <<= 1) {
+                    const uint32_t up = __shfl_up(c, dlt, KN_WAVE);
+                    c += lane >= dlt ? up : 0u;
+                }
+                if (lane == KN_WAVE - 1) {
+                    s_wave[wave] = c;
+                }
+            }
+            __syncthreads();
+            if (tid < 256) {
+                for (int w = 0; w < wave; w++) {
+                    c += s_wave[w];
+                }
+                if (c >= need && c - h < need) {
+                    s_prefix = prefix | ((uint32_t)tid << shift);
+                    s_need = need - (c - h);
+                }
+            }
+            __syncthreads();
+            prefix = s_prefix;
+            need = s_need;
+            prefix_mask |= 0xffu << shift;
+            __syncthreads();
+        }
+        T = prefix;
+    }
+    // b entries are better than T; `need` of the entries equal to T complete the keff
+    const int b = keff - (int)need;
+    int nties = 0;
+    if (T != OT_ABSENT) {
+        // ---- 2. eligible ties: key == T among the first k arrivals with key <= T, their ids -> LDS ----
+        if (tid == 0) {
+            s_count = 0;
+        }
+        __syncthreads();
+        int64_t seen = 0;
+        for (int64_t i0 = 0; i0 < n && seen < k; i0 += OT_THREADS) {
+            const int64_t i = i0 + tid;
+            uint32_t key = OT_ABSENT;
+            int64_t col = 0;
+            if (i < n) {
+                col = col_of(i);
+                key = ot_key<IS_L2>(a, row, rowbase, col);
+            }
+            const bool qual = key <= T;
+            const unsigned long long bal = __ballot(qual);
+            if (lane == 0) {
+                s_wave[wave] = (uint32_t)__popcll(bal);
+            }
+            __syncthreads();
+            uint32_t before = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)), tot = 0;
+            for (int w = 0; w < OT_WAVES; w++) {
+                const uint32_t v = s_wave[w];
+                before += w < wave ? v : 0u;
+                tot += v;
+            }
+            const bool elig = qual && key == T && seen + before < k;
+            const unsigned long long eb = __ballot(elig);
+            uint32_t base = 0;
+            if (eb != 0ull) {
+                if (lane == 0) {
+                    base = atomicAdd(&s_count, (uint32_t)__popcll(eb));
+                }
+                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+            }
+            if (elig) {
+                cand[base + __popcll(eb & ((1ull << lane) - 1ull))] = ot_idkey<IS_L2>(ot_id_of(a, q, rowbase, col));
+            }
+            seen += tot;
+            __syncthreads(); // (s_wave is rewritten by the next tile)
+        }
+        __syncthreads();
+        nties = (int)s_count; // need <= nties <= k
+        const int tp = ot_pow2(nties);
+        for (int j = nties + tid; j < tp; j += OT_THREADS) {
+            cand[j] = ~0ull;
+        }
+        __syncthreads();
+        ot_sort(cand, tp);
+        const float v = rs_unkey<IS_L2>(T);
+        for (int j = tid; j < (int)need && j < nties; j += OT_THREADS) {
+            od[b + j] = v;
+            oi[b + j] = ot_unidkey<IS_L2>(cand[j]);
+        }
+        __syncthreads();
+    }
+    const int nres = T != OT_ABSENT ? b + min((int)need, nties) : b;
+    // ---- 3. the better entries ----
+    if (b > 0) {
+        if (tid == 0) {
+            s_count = 0;
+        }
+        __syncthreads();
+        for (int64_t i0 = 0; i0 < n; i0 += OT_THREADS) {
+            const int64_t i = i0 + tid;
+            const uint32_t key = i < n ? ot_key<IS_L2>(a, row, rowbase, i) : OT_ABSENT;
+            const bool better = key < T;
+            const unsigned long long bb = __ballot(better);
+            uint32_t base = 0;
+            if (bb != 0ull) {
+                if (lane == 0) {
+                    base = atomicAdd(&s_count, (uint32_t)__popcll(bb));
+                }
+                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+            }
+            if (better) {
+                cand[base + __popcll(bb & ((1ull << lane) - 1ull))] = ((unsigned long long)key << 32) | (uint32_t)i;
+            }
+        }
+        __syncthreads();
+        const int bp = ot_pow2(b);
+        // ids of the entries -> LDS (sorted), entries -> scratch
+        for (int j = tid; j < bp; j += OT_THREADS) {
+            if (j < b) {
+                const unsigned long long e = cand[j];
+                const unsigned long long idk = ot_idkey<IS_L2>(ot_id_of(a, q, rowbase, (int64_t)(uint32_t)e));
+                S0[j] = idk;
+                S1[j] = e >> 32;
+                cand[j] = idk;
+            } else {
+                cand[j] = ~0ull;
+            }
+        }
+        __syncthreads();
+        ot_sort(cand, bp);
+        for (int j = tid; j < b; j += OT_THREADS) { // rank of the entry's id
+            const unsigned long long idk = S0[j];
+            int lo = 0, hi = b;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (cand[mid] < idk) {
+                    lo = mid + 1;
+                } else {
+                    hi = mid;
+                }
+            }
+            S1[j] = (S1[j] << 32) | (uint32_t)lo;
+        }
+        __syncthreads();
+        for (int j = tid; j < b; j += OT_THREADS) {
+            S0[j] = cand[j]; // ids in canonical order
+        }
+        __syncthreads();
+        for (int j = tid; j < bp; j += OT_THREADS) {
+            cand[j] = j < b ? S1[j] : ~0ull;
+        }
+        __syncthreads();
+        ot_sort(cand, bp);
+        for (int j = tid; j < b; j += OT_THREADS) {
+            const unsigned long long e = cand[j];
+            od[j] = rs_unkey<IS_L2>((uint32_t)(e >> 32));
+            oi[j] = ot_unidkey<IS_L2>(S0[(uint32_t)e]);
+        }
+    }
+    for (int j = nres + tid; j < k; j += OT_THREADS) {
+        od[j] = worst_dist<IS_L2>();
+        oi[j] = -1;
+    }
+}
+
+int ordered_topk_max_k() {
+    return OT_MAX_K;
+}
+
+size_t ordered_topk_scratch_bytes(int64_t nq, int k) {
+    int64_t kp = 2;
+    while (kp < k) {
+        kp <<= 1;
+    }
+    return (size_t)std::max<int64_t>(nq, 1) * 2 * kp * sizeof(unsigned long long);
+}
+
+hipError_t launch_ordered_topk(const OrdSelArgs& a_in, int64_t nq, bool is_l2, hipStream_t s) {
+    if (nq <= 0) {
+        return hipSuccess;
+    }
+    OrdSelArgs a = a_in;
+    if (a.k <= 0 || a.k > OT_MAX_K || a.scratch == nullptr || a.dist == nullptr || a.out_d == nullptr || a.out_i == nullptr ||
+        a.n_fixed > 0x7fffffffll || (a.seg_col != nullptr && (a.seg_key == nullptr || a.seg_idpos == nullptr || a.nseg <= 0))) {
+        return hipErrorInvalidValue;
+    }
+    a.kp = 2;
+    while (a.kp < a.k) {
+        a.kp <<= 1;
+    }
+    const size_t sm = (size_t)a.kp * 8;
+    auto kern = is_l2 ? ordered_topk_kernel<true> : ordered_topk_kernel<false>;
+    if (sm > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)sm);
+        if (e != hipSuccess) {
+            return e;
+        }
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(OT_THREADS), sm, s, a);
+    return hipGetLastError();
+}
+
 } // namespace knhip

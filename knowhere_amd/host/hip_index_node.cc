@@ -558,6 +558,7 @@ class HipIndexNode : public IndexNode {
         const int64_t k = c.k.value();
         int64_t nprobe = 1;
         if constexpr (Kind != KNHIP_BRUTE_FORCE) nprobe = c.nprobe.value_or(default_nprobe_);
+        if (k > KNHIP_MAX_K) return expected<DataSetPtr>::Err(Status::invalid_args, "k > 16384 is not supported");
         checkCancellation(op_context);
         const float* q = (const float*)dataset->GetTensor();
         std::vector<float> qn;
@@ -594,11 +595,17 @@ class HipIndexNode : public IndexNode {
                 if (has_refine_ && (sh_[0].raw.p || sh_[0].rows.p) && c.refine_k.has_value()) {
                     use_refine = true;
                     const int64_t want = std::max<int64_t>(k, (int64_t)(k * c.refine_k.value()));
-                    kbase = std::min<int64_t>(1024, want);
-                    if (kbase < want) {  // (the first stage returns at most 1024 candidates per query: said, not hidden)
+                    kbase = std::min<int64_t>(KNHIP_MAX_K, want);
+                    if (kbase < want) {  // (the first stage returns at most 16384 candidates per query: said, not hidden)
                         LOG_KNOWHERE_WARNING_ << "GPU_HIP refine: k * refine_k = " << want << " clamped to " << kbase;
                     }
                 }
+            }
+            if (sh_.size() > 1 && std::max(k, kbase) > 1024) {
+                // (the large-k path is one index's: the shard group's merge and tie steps stop at 1024)
+                return expected<DataSetPtr>::Err(Status::not_implemented,
+                                                 "GPU_HIP: k (or k * refine_k) > 1024 is not supported on an index sharded "
+                                                 "with gpu_ids");
             }
             if (sh_.size() > 1) {
                 // list-sharded: every device scans the lists it owns, one all-gather of the partial top-k, device merge

@@ -20,6 +20,12 @@
 #endif
 
 #include <cctype>
+
+#include "../../include/knhip.h"  // KNHIP_MAX_K
+
+// The typed configs admit k up to here (the reference's own config takes any int, config.h:694-698; far beyond it the value
+// is a malformed request: out_of_range_in_json); Search() answers k above KNHIP_MAX_K = 16384 with invalid_args and says so.
+#define KNHIP_CONFIG_MAX_K 65536
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -36,7 +42,7 @@ inline constexpr const char* INDEX_HIP_IVFSQ8 = "GPU_HIP_IVF_SQ8";
 }  // namespace IndexEnum
 
 // ---- configs: the CPU index's config + the limits of this backend, in the style of
-// src/index/gpu_cuvs/gpu_cuvs_ivf_pq_config.h:27-95 (k <= 1024 as the cuVS configs, :49-53) -------------------------
+// src/index/gpu_cuvs/gpu_cuvs_ivf_pq_config.h:27-95 (k: see KNHIP_CONFIG_MAX_K; the cuVS configs stop at 1024, :49-53) -------------------------
 inline Status
 HipCheckMetric(const BaseConfig& cfg, PARAM_TYPE param_type, std::string* err_msg) {
     if (param_type == PARAM_TYPE::TRAIN && cfg.metric_type.has_value()) {
@@ -110,7 +116,7 @@ struct HipBruteForceConfig : public FlatConfig {
         KNOWHERE_CONFIG_DECLARE_FIELD(k)
             .set_default(10)
             .description("search for top k similar vector.")
-            .set_range(1, 1024)
+            .set_range(1, KNHIP_CONFIG_MAX_K)
             .for_search();
     }
     Status
@@ -126,7 +132,7 @@ struct HipIvfFlatConfig : public IvfFlatConfig {
         KNOWHERE_CONFIG_DECLARE_FIELD(k)
             .set_default(10)
             .description("search for top k similar vector.")
-            .set_range(1, 1024)
+            .set_range(1, KNHIP_CONFIG_MAX_K)
             .for_search();
     }
     Status
@@ -142,7 +148,7 @@ struct HipIvfPqConfig : public IvfPqConfig {
         KNOWHERE_CONFIG_DECLARE_FIELD(k)
             .set_default(10)
             .description("search for top k similar vector.")
-            .set_range(1, 1024)
+            .set_range(1, KNHIP_CONFIG_MAX_K)
             .for_search();
         // m = 0: the backend picks (about dim / 2 sub-quantizers, as cuVS does for pq_dim = 0)
         KNOWHERE_CONFIG_DECLARE_FIELD(m).set_default(0).description("m").set_range(0, 65536).for_train();
@@ -181,7 +187,7 @@ struct HipIvfSqConfig : public IvfSqConfig {
         KNOWHERE_CONFIG_DECLARE_FIELD(k)
             .set_default(10)
             .description("search for top k similar vector.")
-            .set_range(1, 1024)
+            .set_range(1, KNHIP_CONFIG_MAX_K)
             .for_search();
     }
     Status

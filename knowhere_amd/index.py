@@ -551,6 +551,29 @@ def tie_resolve(metric, flagged_t, k, can_d_t, can_i_t, arr_d_t, arr_i_t, arr_ke
     return D_t, I_t
 
 
+MAX_K = 16384  # KNHIP_MAX_K: largest k of a search, largest k_base of a refine
+
+
+def select_ordered_device(metric, dist_t, row_len_t, k, ids_t=None, stream=None):
+    """the reference heap's k results of rows of distances given in ARRIVAL order (knhip_select_ordered_device: the
+    selection step of the large-k search and refine).  dist_t [nq, stride] fp32, row_len_t [nq] int64, ids_t [nq, stride]
+    int64 or None (id = column); an entry is absent when its distance is the neutral value / NaN or its id negative.
+    Returns (D [nq, k], I [nq, k]) in heap_reorder order, padded with the neutral distance and id -1."""
+    import torch
+    L = _lib.load()
+    nq, stride = dist_t.shape
+    assert dist_t.is_contiguous() and row_len_t.is_contiguous() and row_len_t.dtype == torch.int64
+    assert ids_t is None or (ids_t.is_contiguous() and ids_t.shape == dist_t.shape and ids_t.dtype == torch.int64)
+    D = torch.empty((nq, k), dtype=torch.float32, device=dist_t.device)
+    I = torch.empty((nq, k), dtype=torch.int64, device=dist_t.device)
+    s = stream
+    if s is None:
+        s = torch.cuda.current_stream(dist_t.device).cuda_stream if dist_t.is_cuda else 0
+    check(L.knhip_select_ordered_device(metric, nq, k, _t_ptr(dist_t), stride, _t_ptr(row_len_t),
+                                        _t_ptr(ids_t) if ids_t is not None else None, _t_ptr(D), _t_ptr(I), C.c_void_p(s)))
+    return D, I
+
+
 def refine_distances_device(metric, base_t, xq_t, cand_ids_t, id_base=0, stream=None):
     """distances of the candidates whose rows live in base_t (row r = id id_base + r); the all-ones pattern elsewhere
     (knhip_refine_distances_device): a shard's share of a sharded refine"""

@@ -1,16 +1,6 @@
-// knowhere_amd/csrc/knhip_api.hip -- the C ABI of libknhip.so (include/knhip.h): index object,
-// HBM layouts, and the Search() orchestration over the kernels in this directory.
-//
-// Search() on the device, IVF kinds (mirrors faiss::IndexIVF::search,
-// reference thirdparty/faiss/faiss/IndexIVF.cpp:305-399, driven per batch instead of per query):
-//   1. coarse   : exact query x centroid distances (flat_full) + per-row top-nprobe (row_select)
-//                 == quantizer->search(n, x, nprobe)                    IndexIVF.cpp:336-342
-//   2. group    : (query, probe) -> list-major work items                worktable.hip
-//   3. tables   : PQ query tables <q_m, cb[m][c]>                        IVFPQ_QueryTables.cpp:56-67
-//   4. scan     : per-list code scan with per-(query, probe) top-k      search_preassigned :625-671
-//   5. merge    : per query, k best of its nprobe partial lists          heap_reorder :665
-// BRUTE_FORCE is steps 4-5 with base chunks in place of lists.
-// Nothing in this path touches the host between the first and the last kernel.
+// knowhere_amd/csrc/knhip_api.hip -- the C ABI of libknhip.so (include/knhip.h): the index object, its HBM layouts and the
+// layouts built on first use (ensure_*), the coarse stage, the workspace pool.  The Search() orchestration over the kernels
+// of this directory is knhip_api_search.hip.
 #include "knhip_internal.h"
 
 namespace knhip_host {
@@ -41,28 +31,9 @@ int build_coarse_layout(knhip_index* idx) {
     return KNHIP_OK;
 }
 
-// Coarse quantizer for one batch: keys/cdis [nq][nprobe], best-first, bit-equal to the exact search.
-// the rows a "nearest rows of every query" stage runs over: the coarse quantizer's centroids, or a chunk of a BRUTE_FORCE base
-struct CoarseRows {
-    const float* rows;      // [n][d] row major
-    const float4* rows_il;  // interleaved 64-row blocks
-    const void* rows_bs;    // split bf16 operand rows (null: the bf16 prefilter is not available)
-    const float* norm;      // [n] ||x||^2
-    float norm_max;
-    int64_t n;
-};
-
-// a search over several row sets one after the other (the chunks of a BRUTE_FORCE base): the k-th best distance found so far
-// bounds what a later chunk can contribute, so only the FIRST chunk needs the two-pass form (group minima -> bound ->
-// candidates); the others take the running k-th, widened by the prefilter's eps, as their selection bound and make ONE pass
-struct RowsRun {
-    float* kth;          // [nq] running k-th best exact distance (worst value before the first chunk)
-    bool have_bound;     // a chunk has been searched: kth bounds this one
-    bool queries_ready;  // the queries' norms and split operand rows of this batch are in the workspace already
-};
-
+// Coarse quantizer for one batch: keys/cdis [nq][nprobe], best-first, bit-equal to the exact search
 int coarse_rows_stage(const knhip_index* idx, Workspace* ws, const CoarseRows& R, const float* d_q, int64_t nq, int nprobe,
-                      int64_t* keys, float* cdis, hipStream_t s, RowsRun* run = nullptr) {
+                      int64_t* keys, float* cdis, hipStream_t s, RowsRun* run) {
     const int64_t nlist = R.n;
     const int d = idx->d;
     const bool is_l2 = idx->is_l2;
@@ -391,8 +362,6 @@ int ensure_mscan_norms(const knhip_index* idx) {
     return KNHIP_OK;
 }
 
-constexpr int KNHIP_PQF_ABANDONED = 1; // (not an error: the selectivity guard sent the batch to the exact kernel)
-
 // IVF-PQ prefilter, every form and the sample pass: per-vector term-2 sums (+ the block offsets they are indexed by), from the
 // canonical AoS codes
 int ensure_psum(const knhip_index* idx) {
@@ -544,1065 +513,13 @@ int ensure_bf_split(const knhip_index* idx) {
     return KNHIP_OK;
 }
 
-// a chunk's (nq, k) result -> slot `slot` of the partial lists [nq][nslots][k], row numbers -> ids
-__global__ void bf_place_kernel(const int64_t* __restrict__ keys, const float* __restrict__ dis, int64_t nq, int k, int64_t add,
-                                float* __restrict__ pd, int64_t* __restrict__ pi, int nslots, int slot) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nq * k) {
-        return;
-    }
-    const int64_t q = t / k, j = t % k;
-    const int64_t o = (q * nslots + slot) * k + j;
-    const int64_t key = keys[t];
-    pd[o] = dis[t];
-    pi[o] = key >= 0 ? key + add : -1;
-}
-
-// rows of a chunk (multiples of 128), 0 = the shape is not served
-static int64_t bf_mfma_chunk_rows(int64_t nb, int k) {
-    const int ncand = k + std::max(32, k / 4);
-    const int64_t nch = (nb + 131071) / 131072;
-    const int64_t per = round_up((nb + nch - 1) / nch, 128);
-    const int64_t last = nb - (nch - 1) * per;
-    if (last <= 0 || !coarse_bf16_supports(per, ncand) || !coarse_bf16_supports(last, ncand) || ncand >= last) {
-        return 0;
-    }
-    return per;
-}
-
-int bf_mfma_batch(const knhip_index* idx, Workspace* ws, const float* d_q, int64_t nq, int k, int64_t per, int64_t* d_out_i,
-                  float* d_out_d, hipStream_t s) {
-    if (int rc = ensure_bf_split(idx)) return rc;
-    const int64_t nb = idx->ntotal;
-    const int d = idx->d;
-    const int nslab = coarse_bf16_slabs(d);
-    const int64_t nch = (nb + per - 1) / per;
-    const int nchunk4 = (d + 3) / 4;
-    // queries per round: the exact fallback's nq x rows scratch stays below 1 GiB
-    const int64_t nqb = std::max<int64_t>(64, std::min<int64_t>(nq, ((int64_t)1 << 28) / per));
-    HIP_TRY(ws->partial_d.reserve((size_t)nq * nch * k * sizeof(float)));
-    HIP_TRY(ws->partial_i.reserve((size_t)nq * nch * k * sizeof(int64_t)));
-    HIP_TRY(ws->keys.reserve((size_t)nqb * k * sizeof(int64_t)));
-    HIP_TRY(ws->cdis.reserve((size_t)nqb * k * sizeof(float)));
-    {
-        StageTimer t(idx, s, KNHIP_STAGE_SCAN);
-        HIP_TRY(ws->bf_kth.reserve((size_t)nqb * sizeof(float)));
-        for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
-            const int64_t n = std::min(nqb, nq - q0);
-            // (one pass over every chunk but the first: the k-th best of the chunks searched so far is the selection bound)
-            HIP_TRY(launch_fill_f32(ws->bf_kth.as<float>(), n, idx->is_l2 ? FLT_MAX : -FLT_MAX, s));
-            RowsRun run{ws->bf_kth.as<float>(), false, false};
-            for (int64_t c = 0; c < nch; c++) {
-                const int64_t r0 = c * per, rn = std::min(per, nb - r0);
-                CoarseRows R{idx->codes_aos.as<float>() + r0 * d, idx->rows.as<float4>() + (r0 / 64) * nchunk4 * 64,
-                             static_cast<const unsigned char*>(idx->rows_bs.p) + (size_t)r0 * nslab * 128,
-                             idx->bf_norm.as<float>() + r0, idx->bf_norm_max, rn};
-                if (int rc = coarse_rows_stage(idx, ws, R, d_q + q0 * d, n, k, ws->keys.as<int64_t>(), ws->cdis.as<float>(), s,
-                                               &run)) {
-                    return rc;
-                }
-                hipLaunchKernelGGL(bf_place_kernel, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, s, ws->keys.as<int64_t>(),
-                                   ws->cdis.as<float>(), n, k, r0 + idx->id_offset, ws->partial_d.as<float>() + q0 * nch * k,
-                                   ws->partial_i.as<int64_t>() + q0 * nch * k, (int)nch, (int)c);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-    }
-    {
-        std::lock_guard<std::mutex> lk(idx->mu);
-        idx->coarse_flops += 0.0; // (the stage's flop count is the bench's: 2 nq nb d)
-    }
-    StageTimer t(idx, s, KNHIP_STAGE_MERGE);
-    HIP_TRY(launch_merge_partials(ws->partial_d.as<float>(), ws->partial_i.as<int64_t>(), nq, (int)nch, k, nch * k, k,
-                                  idx->is_l2, d_out_d, d_out_i, s));
-    return KNHIP_OK;
-}
-
-// ---- one batch of queries, everything on the device ------------------------------------------------
-// pre_keys / pre_cdis non-null: the coarse assignment is given (IndexIVF::search_preassigned), [nq][nprobe]
-int search_batch(const knhip_index* idx, Workspace* ws, const float* d_q, int64_t nq, int k, int nprobe,
-                 const uint8_t* d_bitset, int64_t nbits, int64_t* d_out_i, float* d_out_d,
-                 hipStream_t s, const int64_t* pre_keys, const float* pre_cdis) {
-    const int kind = idx->desc.kind;
-    const int d = idx->d;
-    const bool is_l2 = idx->is_l2;
-    HIP_TRY(ws->gthr.reserve((size_t)nq * sizeof(float)));
-    HIP_TRY(launch_fill_f32(ws->gthr.as<float>(), nq, is_l2 ? FLT_MAX : -FLT_MAX, s));
-
-    if (kind == KNHIP_BRUTE_FORCE) {
-        const int64_t nb = idx->ntotal;
-        if (idx->bf_mfma && d_bitset == nullptr && idx->cos_mode == 0 && idx->coarse_gemm == 2 && nb >= 4096 && nq >= 16 &&
-            (double)nq * (double)nb >= 16.0e6) {
-            const int64_t per = bf_mfma_chunk_rows(nb, k);
-            if (per > 0) {
-                idx->last_bf_mfma = 1;
-                return bf_mfma_batch(idx, ws, d_q, nq, k, per, d_out_i, d_out_d, s);
-            }
-        }
-        idx->last_bf_mfma = 0;
-        int64_t chunk_rows = std::max<int64_t>(1024, round_up((nb + 511) / 512, 64));
-        const int64_t nchunks = (nb + chunk_rows - 1) / chunk_rows;
-        const int qg = flat_scan_qg(k);
-        const int64_t ngroups = (nq + qg - 1) / qg;
-        HIP_TRY(ws->partial_d.reserve((size_t)nq * nchunks * k * sizeof(float)));
-        HIP_TRY(ws->partial_i.reserve((size_t)nq * nchunks * k * sizeof(int64_t)));
-        FlatScanArgs a{};
-        a.rows = idx->rows.as<float4>();
-        a.nrows = nb;
-        a.chunk_rows = chunk_rows;
-        a.id_offset = idx->id_offset;
-        a.d = d;
-        a.nchunk = (d + 3) / 4;
-        a.queries = d_q;
-        a.nq = nq;
-        a.nitems_dense = nchunks * ngroups;
-        a.ngroups = ngroups;
-        a.bitset = d_bitset;
-        a.bitset_nbits = nbits;
-        a.partial_d = ws->partial_d.as<float>();
-        a.partial_i = ws->partial_i.as<int64_t>();
-        a.gthr = ws->gthr.as<float>();
-        a.nslot = (int)nchunks;
-        a.k = k;
-        a.row_scale = idx->row_scale.as<float>();
-        a.cos_mode = idx->cos_mode;
-        {
-            StageTimer t(idx, s, KNHIP_STAGE_SCAN);
-            HIP_TRY(launch_flat_scan(a, is_l2, true, a.nitems_dense, s));
-        }
-        {
-            StageTimer t(idx, s, KNHIP_STAGE_MERGE);
-            HIP_TRY(launch_merge_partials(a.partial_d, a.partial_i, nq, (int)nchunks, k, nchunks * k, k,
-                                          is_l2, d_out_d, d_out_i, s));
-        }
-        return KNHIP_OK;
-    }
-
-    // ---- IVF kinds ----
-    const int64_t nlist = idx->nlist;
-    // 1. coarse
-    const int64_t* keys_p = pre_keys;
-    const float* cdis_p = pre_cdis;
-    if (pre_keys == nullptr) {
-        HIP_TRY(ws->keys.reserve((size_t)nq * nprobe * sizeof(int64_t)));
-        HIP_TRY(ws->cdis.reserve((size_t)nq * nprobe * sizeof(float)));
-        StageTimer t(idx, s, KNHIP_STAGE_COARSE);
-        if (int rc = coarse_stage(idx, ws, d_q, nq, nprobe, ws->keys.as<int64_t>(), ws->cdis.as<float>(), s)) {
-            return rc;
-        }
-        keys_p = ws->keys.as<int64_t>();
-        cdis_p = ws->cdis.as<float>();
-    }
-    if (kind == KNHIP_IVF_PQ && !pq_scan_supported_m(idx->desc.pq_m)) {
-        // any other number of sub-quantizers: the plain exact kernel, one workgroup per (query, probe), no work table
-        const int M = idx->desc.pq_m;
-        const int mode = !is_l2 ? PQ_LUT_IP : (idx->use_precomp ? PQ_LUT_PRECOMP : PQ_LUT_RESIDUAL);
-        if (mode != PQ_LUT_RESIDUAL) {
-            HIP_TRY(ws->t2t.reserve((size_t)nq * 256 * M * sizeof(float)));
-            StageTimer t(idx, s, KNHIP_STAGE_LUT);
-            HIP_TRY(launch_pq_query_table(d_q, idx->cb.as<float>(), d, M, nq, ws->t2t.as<float>(), s));
-        }
-        const int64_t nparts = (int64_t)nprobe * pq_scan_any_parts(k);
-        HIP_TRY(ws->partial_d.reserve((size_t)nq * nparts * k * sizeof(float)));
-        HIP_TRY(ws->partial_i.reserve((size_t)nq * nparts * k * sizeof(int64_t)));
-        PqAnyArgs a{};
-        a.keys = keys_p;
-        a.coarse_dis = cdis_p;
-        a.nprobe = nprobe;
-        a.nlist = nlist;
-        a.list_len = idx->d_list_len.as<int64_t>();
-        a.list_row_off = idx->d_list_row_off.as<int64_t>();
-        a.codes = idx->codes_aos.as<uint8_t>();
-        a.ids = idx->ids.as<int64_t>();
-        a.M = M;
-        a.d = d;
-        a.lut_mode = mode;
-        a.t2t = ws->t2t.as<float>();
-        a.precomp_t = idx->precomp_t.as<float>();
-        a.cb = idx->cb.as<float>();
-        a.centroids = idx->centroids.as<float>();
-        a.queries = d_q;
-        a.bitset = d_bitset;
-        a.bitset_nbits = nbits;
-        a.partial_d = ws->partial_d.as<float>();
-        a.partial_i = ws->partial_i.as<int64_t>();
-        a.k = k;
-        {
-            StageTimer t(idx, s, KNHIP_STAGE_SCAN);
-            HIP_TRY(launch_pq_scan_any(a, nq, is_l2, s));
-        }
-        StageTimer t(idx, s, KNHIP_STAGE_MERGE);
-        HIP_TRY(launch_merge_partials(a.partial_d, a.partial_i, nq, (int)nparts, k, nparts * k, k, is_l2, d_out_d, d_out_i, s));
-        return KNHIP_OK;
-    }
-    // 2. group
-    const int qg = (kind == KNHIP_IVF_PQ) ? pq_scan_qg(idx->desc.pq_m)
-                 : (kind == KNHIP_IVF_SQ8) ? sq_scan_qg(k)
-                                           : flat_scan_qg(k);
-    const int64_t npairs = nq * nprobe;
-    // IVF-PQ m = 32: which kernels run the two phases (rank-0 dump + select, bulk) and how many queries they
-    // take per work item
-    bool pq_use_v2 = false, pq_rank0 = false, pq_use_q4 = false;
-    int qg_rank0 = qg, qg_bulk = qg;
-    if (kind == KNHIP_IVF_PQ && idx->pq_v2 && pq_scan_v2_supports(idx->desc.pq_m, k)) {
-        pq_use_v2 = true;
-        const int64_t stride = round_up(std::max<int64_t>(idx->max_list_len, 64), 64);
-        // (worth it once k is large enough that sorted insertion dominates: measured k >= 32)
-        pq_rank0 = idx->rank0_select && k >= 32 && nprobe > 1 && (double)nq * stride * 4.0 <= 6.0e9;
-        // the 4-query kernel pays when the lists are shared by enough (query, probe) pairs of the batch
-        pq_use_q4 = idx->cb_t.p != nullptr && pq_scan_q4_supports(idx->desc.pq_m, d, k) &&
-                (idx->pq_q4 == 1 || (idx->pq_q4 == 2 && npairs >= 6 * nlist));
-        if (pq_use_q4) {
-            qg_bulk = 4;
-            qg_rank0 = pq_rank0 ? qg : 4;
-        }
-    }
-    // IVF-Flat / IVF-SQ8: MFMA prefilter + exact finish (mfma_scan.hip) when the lists are shared by enough queries.
-    // IVF-PQ m = 32: the matrix-core ADC prefilter (pq_filter.hip) through the same machinery, when the lists are shared by
-    // enough queries for its units of (list, 8 queries) -- 4 pairs per list on average --; its exact fallback is the
-    // 4-query kernel.
-    bool use_ms = false;
-    int ms_cap = 0, ms_nchunk = 0, ms_nstep = 0;
-    // (k <= 128: the exact fallback of its overflowed queries is the 4-query kernel; 128 < k <= 1024 -- Knowhere's refine
-    // asks for k * refine_k candidates -- it is the systolic kernel over one-pair items: the filter, the sample and the
-    // finish take any k)
-    const bool pq_q4_ok = kind == KNHIP_IVF_PQ && pq_scan_q4_supports(idx->desc.pq_m, d, k);
-    const bool pqf_shape = kind == KNHIP_IVF_PQ && idx->pqf != 0 && idx->pq_v2 && idx->cb_t.p != nullptr &&
-            pqf_supports(idx->desc.pq_m, d) && k <= 1024 && (pq_q4_ok || pq_scan_supported_m(idx->desc.pq_m)) &&
-            (!is_l2 || idx->use_precomp); // (residual tables: see pq_psum_kernel)
-    // (COSINE with stored norms takes the exact kernels: the prefilter's bound does not carry the per-row division)
-    if ((kind == KNHIP_IVF_FLAT || kind == KNHIP_IVF_SQ8 || pqf_shape) && (idx->mscan != 0 || pqf_shape) && nprobe >= 2 &&
-        idx->cos_mode == 0) {
-        size_t lds;
-        if (kind == KNHIP_IVF_PQ) {
-            ms_nchunk = d / 4;
-            lds = pqf_smem();
-        } else if (kind == KNHIP_IVF_FLAT) {
-            ms_nchunk = (d + 3) / 4;
-            ms_nstep = (ms_nchunk + 3) / 4;
-            lds = mscan_flat_smem(ms_nstep);
-        } else {
-            const int step_chunks = idx->sq_bits == 6 ? 3 : 2; // (sq_codec.h SqStep: 32 dims for 8 bits, 64 for 6 and 4)
-            ms_nchunk = sq_nchunk16(d, idx->sq_bits);
-            ms_nstep = (ms_nchunk + step_chunks - 1) / step_chunks;
-            lds = mscan_sq8_smem(ms_nstep, idx->sq_bits);
-        }
-        // candidate capacity per query: the finish kernel sorts them in LDS (a power of two entries)
-        // candidate capacity per query (the finish kernel takes any number, in chunks): generous -- a query whose sample
-        // gave a loose bound collects thousands of rows before its histogram tightens it, and their exact distances
-        // cost far less than the exact scan of all its lists -- within ~3 GB of scratch per batch
-        ms_cap = 4096;
-        while (ms_cap < (int64_t)16 * nprobe * k && ms_cap < 32768) {
-            ms_cap <<= 1;
-        }
-        while (ms_cap > 1024 && (double)ms_cap * (double)nq * 8.0 > 3.0e9) {
-            ms_cap >>= 1;
-        }
-        if (idx->mscan_cap > 0) {
-            ms_cap = idx->mscan_cap;
-        }
-        use_ms = lds <= 160 * 1024 - 1024 && ms_cap >= 2 * k &&
-                (kind == KNHIP_IVF_PQ ? (idx->pqf == 2 || npairs >= 4 * nlist) : (idx->mscan == 1 || npairs >= 8 * nlist));
-    }
-    if (use_ms && kind == KNHIP_IVF_PQ) { // (no rank-0 dump phase: the sample pass of the prefilter gives the bounds)
-        pq_rank0 = false;
-        pq_use_q4 = pq_q4_ok;
-        qg_bulk = pq_q4_ok ? 4 : qg;
-        qg_rank0 = pq_q4_ok ? 4 : qg;
-    }
-    const int64_t items_bound =
-            round_up(npairs / std::min(qg_rank0, qg_bulk) + std::min<int64_t>(2 * nlist, npairs) + 1, 8);
-    HIP_TRY(ws->list_count.reserve((size_t)2 * nlist * sizeof(int32_t)));
-    HIP_TRY(ws->list_cursor.reserve((size_t)2 * nlist * sizeof(int32_t)));
-    HIP_TRY(ws->list_pair_off.reserve((size_t)(2 * nlist + 1) * sizeof(int64_t)));
-    HIP_TRY(ws->list_item_off.reserve((size_t)(2 * nlist + 1) * sizeof(int64_t)));
-    HIP_TRY(ws->pairs.reserve((size_t)npairs * sizeof(KnPair)));
-    // (the MFMA prefilter's fallback compacts the pairs of overflowed queries into one-query items: up to npairs)
-    HIP_TRY(ws->items.reserve((size_t)(use_ms ? std::max<int64_t>(npairs, items_bound) : items_bound) * sizeof(KnItem)));
-    HIP_TRY(ws->nitems.reserve(sizeof(int64_t)));
-    // rows of a query's sample (IVF-Flat / IVF-SQ8 prefilter), at most: the first max(1024, 8 k) rows of its closest
-    // list(s) -- the pass is bound by the rows it reads (C2: every list is somebody's closest: the whole index once per
-    // batch when a list was sampled in full), and tau from 1024 rows lets only a few dozen more candidates through.
-    // KNHIP_MS_SAMPLE_ROWS=n overrides (tests / experiments; 8192 = whole lists as in rounds 2-4)
-    // (IVF-SQ8 too, now that its finish prunes: before that the looser tau cost C5's finish 2.7 ms for 1.1 ms saved here)
-    int ms_sample_cap = std::min<int>(mscan_sample_rows(), (std::max(1024, 8 * k) + 63) / 64 * 64);
-    const EnvSearch env = env_search(); // (the switches every search reads: knhip_env.h)
-    if (env.ms_sample_rows > 0) {
-        ms_sample_cap = std::max(64, std::min(mscan_sample_rows(), env.ms_sample_rows / 64 * 64));
-    }
-    WorkTable wt{};
-    wt.list_count = ws->list_count.as<int32_t>();
-    wt.list_cursor = ws->list_cursor.as<int32_t>();
-    wt.list_pair_off = ws->list_pair_off.as<int64_t>();
-    wt.list_item_off = ws->list_item_off.as<int64_t>();
-    wt.pairs = ws->pairs.as<KnPair>();
-    wt.items = ws->items.as<KnItem>();
-    wt.nitems = ws->nitems.as<int64_t>();
-    wt.scan_bytes = idx->scan_bytes_dev.as<double>();
-    HIP_TRY(ws->partial_d.reserve((size_t)npairs * k * sizeof(float)));
-    HIP_TRY(ws->partial_i.reserve((size_t)npairs * k * sizeof(int64_t)));
-    wt.empty_mark = ws->partial_i.as<int64_t>();
-    wt.k = k;
-    // The IVF-PQ prefilter samples per query (pq_filter.hip, pq_sample_kernel) and groups all probes of a list together
-    // afterwards: it needs this table -- split by the sample plan -- only when its guard abandons the batch.
-    const bool wt1_lazy = use_ms && kind == KNHIP_IVF_PQ;
-    auto build_wt1 = [&]() -> int {
-        StageTimer t(idx, s, KNHIP_STAGE_GROUP);
-        const int32_t* cls = nullptr;
-        if (use_ms) {
-            // the first class of the split = the pairs whose rows feed tau_q (mfma_scan.hip sample plan): the probes in
-            // coarse order until max(1024, 8 k) rows are covered
-            HIP_TRY(ws->ms_sample_off.reserve((size_t)npairs * sizeof(int32_t)));
-            HIP_TRY(ws->ms_nrow.reserve((size_t)nq * sizeof(int32_t)));
-            HIP_TRY(launch_ms_sample_plan(keys_p, nq, nprobe, nlist, idx->d_list_len.as<int64_t>(),
-                                          std::max(1024, 8 * k), ms_sample_cap, ws->ms_sample_off.as<int32_t>(),
-                                          ws->ms_nrow.as<int32_t>(), s));
-            cls = ws->ms_sample_off.as<int32_t>();
-        }
-        HIP_TRY(launch_build_worktable(keys_p, nq, nprobe, nlist, qg_rank0, qg_bulk,
-                                       idx->d_list_len.as<int64_t>(), idx->code_size, wt, s, 0, cls));
-        return KNHIP_OK;
-    };
-    if (!wt1_lazy) {
-        if (int rc = build_wt1()) return rc;
-    }
-    {
-        std::lock_guard<std::mutex> lk(idx->mu);
-        idx->last_items_bound = items_bound;
-    }
-
-    // The MFMA prefilter path (mfma_scan.hip): sample -> tau_q, filter, exact finish; `exact_one` runs the exact kernel
-    // over a compact table of one-query items (the overflowed queries; normally none, the kernels then return at once)
-    auto run_mscan = [&](const std::function<int(const KnItem*, const KnPair*, const int64_t*, int64_t)>& exact_one)
-            -> int {
-        if (kind == KNHIP_IVF_PQ) {
-            if (int rc = ensure_psum(idx)) return rc; // (the token streams / the half codebook follow the form)
-        } else {
-            if (int rc = ensure_mscan_norms(idx)) return rc;
-        }
-        int qt = mscan_queries_per_unit(kind, false);
-        // IVF-Flat: the filter pass on the bf16 matrix pipe (mfma_scan_bf16.hip: up to 128 queries per unit); the sample
-        // pass stays on the fp32 kernel (its units hold one or two queries: bound by the rows it reads, not by the products)
-        const bool flat_b = kind == KNHIP_IVF_FLAT && idx->flat_bf16 && mscan_flat_bf16_qt(ms_nstep) > 0;
-        if (flat_b) {
-            qt = mscan_flat_bf16_qt(ms_nstep);
-        }
-        const int qt0 = mscan_queries_per_unit(kind, true);
-        const int64_t units_bound = round_up(npairs / qt + std::min<int64_t>(nlist, npairs) + 1, 8);
-        const int64_t sample = mscan_sample_rows();
-        // (a query samples at most `sample` rows of non-empty lists: at most that many pairs)
-        const int64_t np0 = std::min<int64_t>(npairs, nq * std::min<int64_t>(nprobe, sample));
-        const int64_t bound0 = round_up(np0 / qt0 + std::min<int64_t>(nlist, np0) + 1, 8);
-        HIP_TRY(ws->ms_units.reserve((size_t)std::max(units_bound, bound0) * sizeof(KnItem)));
-        HIP_TRY(ws->ms_unit_off.reserve((size_t)(nlist + 1) * sizeof(int64_t)));
-        HIP_TRY(ws->ms_nunits.reserve(sizeof(int64_t) + 2 * sizeof(double)));
-        HIP_TRY(ws->ms_cand.reserve((size_t)nq * ms_cap * sizeof(int64_t)));
-        HIP_TRY(ws->ms_cand_pess.reserve((size_t)nq * ms_cap * sizeof(float)));
-        if (kind == KNHIP_IVF_SQ8) {
-            HIP_TRY(ws->ms_eps_max.reserve((size_t)nq * sizeof(uint32_t)));
-            HIP_TRY(hipMemsetAsync(ws->ms_eps_max.p, 0, (size_t)nq * sizeof(uint32_t), s));
-        }
-        HIP_TRY(ws->ms_cand_cnt.reserve((size_t)(2 * nq + 4) * sizeof(int32_t))); // counters, flags, any-flag, guard counters
-        HIP_TRY(ws->dump.reserve((size_t)nq * sample * sizeof(float)));
-        HIP_TRY(ws->sel_keys.reserve((size_t)nq * k * sizeof(int64_t)));
-        HIP_TRY(ws->sel_d.reserve((size_t)nq * k * sizeof(float)));
-        HIP_TRY(ws->ghist.reserve((size_t)nq * 64 * sizeof(uint32_t)));
-        HIP_TRY(ws->gmeta.reserve((size_t)nq * sizeof(uint2)));
-        int32_t* cand_cnt = ws->ms_cand_cnt.as<int32_t>();
-        int32_t* overflow = cand_cnt + nq;
-        MScanArgs m{};
-        m.rows = idx->rows.p;
-        m.xnorm = idx->xnorm.as<float>();
-        m.xnorm_max = idx->xnorm_max;
-        m.list_blk_off = idx->d_list_blk_off.as<int64_t>();
-        m.list_len = idx->d_list_len.as<int64_t>();
-        m.list_row_off = idx->d_list_row_off.as<int64_t>();
-        m.ids = idx->ids.as<int64_t>();
-        m.trained = idx->sq_trained.as<float>();
-        m.centroids = idx->centroids.as<float>();
-        m.d = d;
-        m.nchunk = ms_nchunk;
-        m.nstep = ms_nstep;
-        m.sq_bits = kind == KNHIP_IVF_SQ8 ? idx->sq_bits : 0;
-        m.queries = d_q;
-        m.qnorm = ws->qnorm.as<float>();
-        m.coarse_dis = cdis_p;
-        m.nq = nq;
-        m.nslot = nprobe;
-        m.units = ws->ms_units.as<KnItem>();
-        m.pairs = wt.pairs;
-        m.nunits_dev = ws->ms_nunits.as<int64_t>();
-        m.gthr = ws->gthr.as<float>();
-        // |approx - exact| <= eps_scale * magnitude: see mfma_scan.hip
-        const float eps_fp32 = (kind == KNHIP_IVF_FLAT ? 16.0f : 32.0f) * (float)d * 5.9604645e-8f;
-        // (split-bf16 products drop lo lo + r_q x + q r_x <= 3 * 2^-16 ||q|| ||x||: mfma_scan_bf16.hip)
-        m.eps_scale = eps_fp32 + (flat_b ? 6.103515625e-5f : 0.f);
-        m.bitset = d_bitset;
-        m.bitset_nbits = nbits;
-        m.cand_cnt = cand_cnt;
-        m.cand = ws->ms_cand.as<int64_t>();
-        m.cand_pess = ws->ms_cand_pess.as<float>();
-        m.eps_max = kind == KNHIP_IVF_SQ8 ? ws->ms_eps_max.as<uint32_t>() : nullptr;
-        m.cap = ms_cap;
-        m.overflow = overflow;
-        m.gthr_rw = ws->gthr.as<float>();
-        m.k = k;
-        if (idx->cand_hist) {
-            m.ghist = ws->ghist.as<uint32_t>();
-            m.gmeta = ws->gmeta.as<uint2>();
-        }
-        if (kind == KNHIP_IVF_PQ) {
-            // (retry round: one-query units, up to one per pair)
-            HIP_TRY(ws->pq_recs.reserve((size_t)std::max<int64_t>(std::max(units_bound, bound0), npairs) * sizeof(P8Rec)));
-            HIP_TRY(ws->pq_ctr.reserve(8 * 16 * sizeof(int32_t)));
-            m.list_blk_off = nullptr;
-            m.pq_sblk_off_r = idx->d_list_blk_off_r.as<int64_t>();
-            m.pq_psum = idx->psum.as<float>();
-            m.pq_cb_t = idx->cb_t.as<float4>();
-            m.pq_precomp_t = idx->precomp_t.as<float>();
-            m.pq_codes = idx->codes_aos.as<uint8_t>();
-            m.pq_lut_mode = !is_l2 ? PQ_LUT_IP : (idx->use_precomp ? PQ_LUT_PRECOMP : PQ_LUT_RESIDUAL);
-            m.pq_recs = ws->pq_recs.as<P8Rec>();
-            m.pq_ctr = ws->pq_ctr.as<int32_t>();
-        }
-        bool pq_i8 = false; // IVF-PQ: the integer form of the filter (chosen after the sample pass)
-        bool pq_dec = false; // IVF-PQ: the decode form (pq_decode.hip)
-        int pqd_cost = 0;    // ... its units' cost cap (0: list-long units) and their number, at most
-        int64_t pqd_bound = 0;
-        // which second form the guard weighs against the half tables: the decode form (default; its eps lies between the
-        // half tables' and the int8 tables', its units hold 128 queries) or, when asked for, the int8 tables
-        const bool pqd_ok = kind == KNHIP_IVF_PQ && pqd_supports(idx->desc.pq_m, d);
-        const bool want_dec = kind == KNHIP_IVF_PQ && pqd_ok && (idx->pqf_form == 0 || idx->pqf_form == 3);
-        // IVF-PQ: the pairs are grouped by list (work table: four small, latency-bound kernels, ~0.25 ms per 10^4 queries at
-        // C3) on a side stream while this stream runs the sample pass; only the cut into units waits for the form.
-        SideJoin sj{ws, s};
-        WorkTable wside = wt; // the table the filter pass reads (its own buffers when it is built on the side stream)
-        if (!wt1_lazy && !env.no_side_stream) {
-            // IVF-Flat / IVF-SQ8: the sample pass reads the split table built above; the all-probes table of the filter pass
-            // goes to a second set of buffers and is built beside the sample pass (0.35 ms per batch at C2, 1.5 ms at C5)
-            HIP_TRY(ws->list_count2.reserve((size_t)2 * nlist * sizeof(int32_t)));
-            HIP_TRY(ws->list_cursor2.reserve((size_t)2 * nlist * sizeof(int32_t)));
-            HIP_TRY(ws->list_pair_off2.reserve((size_t)(2 * nlist + 1) * sizeof(int64_t)));
-            HIP_TRY(ws->list_item_off2.reserve((size_t)(2 * nlist + 1) * sizeof(int64_t)));
-            HIP_TRY(ws->pairs2.reserve((size_t)npairs * sizeof(KnPair)));
-            HIP_TRY(ws->items2.reserve((size_t)items_bound * sizeof(KnItem)));
-            HIP_TRY(ws->nitems2.reserve(sizeof(int64_t)));
-            wside.list_count = ws->list_count2.as<int32_t>();
-            wside.list_cursor = ws->list_cursor2.as<int32_t>();
-            wside.list_pair_off = ws->list_pair_off2.as<int64_t>();
-            wside.list_item_off = ws->list_item_off2.as<int64_t>();
-            wside.pairs = ws->pairs2.as<KnPair>();
-            wside.items = ws->items2.as<KnItem>();
-            wside.nitems = ws->nitems2.as<int64_t>();
-            wside.scan_bytes = reinterpret_cast<double*>(ws->ms_nunits.as<int64_t>() + 1); // (bytes were counted above)
-            if (ws->side == nullptr) {
-                HIP_TRY(hipStreamCreateWithFlags(&ws->side, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&ws->ev_fork, hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&ws->ev_join, hipEventDisableTiming));
-            }
-            HIP_TRY(hipEventRecord(ws->ev_fork, s));
-            HIP_TRY(hipStreamWaitEvent(ws->side, ws->ev_fork, 0));
-            HIP_TRY(launch_build_worktable(keys_p, nq, nprobe, nlist, qg, qg, idx->d_list_len.as<int64_t>(),
-                                           idx->code_size, wside, ws->side, /*rank0_slot=*/-1));
-            HIP_TRY(hipEventRecord(ws->ev_join, ws->side));
-            sj.forked = true;
-        }
-        if (wt1_lazy && !env.no_side_stream) {
-            if (ws->side == nullptr) {
-                HIP_TRY(hipStreamCreateWithFlags(&ws->side, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&ws->ev_fork, hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&ws->ev_join, hipEventDisableTiming));
-            }
-            HIP_TRY(hipEventRecord(ws->ev_fork, s));
-            HIP_TRY(hipStreamWaitEvent(ws->side, ws->ev_fork, 0));
-            WorkTable w2 = wt;
-            HIP_TRY(launch_build_worktable(keys_p, nq, nprobe, nlist, qg, qg, idx->d_list_len.as<int64_t>(),
-                                           idx->code_size, w2, ws->side, /*rank0_slot=*/-1));
-            HIP_TRY(hipEventRecord(ws->ev_join, ws->side));
-            sj.forked = true;
-        }
-        const bool wt2_done = sj.forked;
-        auto launch_filter = [&](const MScanArgs& x, int64_t bound) -> hipError_t {
-            return kind == KNHIP_IVF_FLAT ? ((flat_b && x.dump == nullptr) ? launch_mscan_flat_bf16(x, is_l2, bound, s)
-                                                                            : launch_mscan_flat(x, is_l2, bound, s))
-                 : kind == KNHIP_IVF_SQ8  ? launch_mscan_sq8(x, is_l2, bound, s)
-                 : (pq_dec && x.dump == nullptr) ? launch_pqd(x, is_l2, bound, s)
-                 : (pq_i8 && x.dump == nullptr)  ? launch_pqi(x, is_l2, bound, s)
-                                                 : launch_pqf(x, is_l2, bound, s);
-        };
-        idx->rank0_phase_used = false;
-        idx->last_pq_form = 0;
-        {
-            // phase 1: tau_q from a sample of the closest list (units of the rank-0 virtual lists [0, nlist), DUMP mode)
-            StageTimer t(idx, s, KNHIP_STAGE_SCAN_RANK0);
-            HIP_TRY(hipMemsetAsync(cand_cnt, 0, (size_t)(2 * nq + 1) * sizeof(int32_t), s));
-            const bool want_i8 = kind == KNHIP_IVF_PQ && idx->pqf_form == 2;
-            if (kind == KNHIP_IVF_PQ) {
-                // (the sample pass below computes the queries' table statistics; the tables themselves follow the guard)
-                HIP_TRY(ws->ms_qs.reserve((size_t)nq * 4 * sizeof(float)));
-                HIP_TRY(ws->ms_nrow.reserve((size_t)nq * sizeof(int32_t)));
-                m.pq_qs = ws->ms_qs.as<float>();
-                if (want_i8) {
-                    HIP_TRY(ws->ms_qi.reserve((size_t)nq * 256 * 32));
-                    HIP_TRY(ws->ms_qis.reserve(((size_t)nq * 4 + 4) * sizeof(float))); // (+ the batch record)
-                    HIP_TRY(ws->ms_qmu.reserve((size_t)nq * 32 * sizeof(float)));
-                }
-            } else if (kind == KNHIP_IVF_FLAT) {
-                HIP_TRY(ws->qnorm.reserve((size_t)nq * sizeof(float)));
-                m.qnorm = ws->qnorm.as<float>();
-                HIP_TRY(launch_row_norms(d_q, nq, d, ws->qnorm.as<float>(), s));
-            } else if (!is_l2) {
-                // inner product: the query operand (scaled, split into two halves) is the same for every list
-                const int ldq = ms_nstep * (idx->sq_bits == 8 ? 32 : 64);
-                HIP_TRY(ws->ms_qh.reserve((size_t)nq * ldq * 2));
-                HIP_TRY(ws->ms_ql.reserve((size_t)nq * ldq * 2));
-                HIP_TRY(ws->ms_qs.reserve((size_t)nq * 8 * sizeof(float)));
-                HIP_TRY(launch_ms_sq8_query_prep(d_q, nq, d, ldq, idx->sq_trained.as<float>(), ws->ms_qh.p, ws->ms_ql.p,
-                                                 ws->ms_qs.as<float>(), s, idx->sq_bits));
-                m.qh = ws->ms_qh.p;
-                m.ql = ws->ms_ql.p;
-                m.qs = ws->ms_qs.as<float>();
-            }
-            HIP_TRY(hipMemsetAsync(ws->ghist.p, 0, (size_t)nq * 64 * sizeof(uint32_t), s));
-            MScanArgs ds = m;
-            ds.eps_scale = eps_fp32; // (the sample pass runs the fp32 kernel)
-            ds.dump = ws->dump.as<float>();
-            ds.dump_stride = sample;
-            ds.sample_cap = ms_sample_cap;
-            ds.ghist = nullptr;
-            if (kind == KNHIP_IVF_PQ) {
-                // one workgroup per query: plan, fp32 table, sampled rows, and the statistics of both table forms
-                int scap = (int)sample;
-                if (env.pq_sample_rows > 0) { // (experiments: rows of the sample, at most)
-                    scap = std::max(64, std::min((int)sample, env.pq_sample_rows));
-                }
-                HIP_TRY(launch_pq_sample(ds, keys_p, idx->cb.as<float4>(), nlist, std::max(1024, 8 * k), scap,
-                                         idx->pabs_max, is_l2, ws->ms_nrow.as<int32_t>(), ws->ms_qs.as<float>(),
-                                         want_i8 ? ws->ms_qis.as<float>() : nullptr,
-                                         want_i8 ? ws->ms_qmu.as<float>() : nullptr, s, ws->gthr.as<float>(),
-                                         ws->gmeta.as<uint2>(), k)); // (tau_q and the histogram range come out of it too)
-            } else {
-                HIP_TRY(launch_ms_units(wt.list_count, wt.list_pair_off, nlist, qt0, ws->ms_unit_off.as<int64_t>(),
-                                        ws->ms_nunits.as<int64_t>(), ws->ms_units.as<KnItem>(),
-                                        idx->d_list_len.as<int64_t>(), idx->code_size, nullptr, s));
-                ds.sample_off = ws->ms_sample_off.as<int32_t>();
-                HIP_TRY(launch_filter(ds, bound0));
-            }
-            if (kind != KNHIP_IVF_PQ) {
-                HIP_TRY(launch_row_select_var(ws->dump.as<float>(), sample, keys_p, nprobe, idx->d_list_len.as<int64_t>(),
-                                              nq, k, is_l2, ws->sel_keys.as<int64_t>(), ws->sel_d.as<float>(), s, sample,
-                                              ws->ms_nrow.as<int32_t>()));
-                HIP_TRY(launch_ms_tau(ws->sel_d.as<float>(), nq, k, is_l2, ws->gthr.as<float>(), ws->gmeta.as<uint2>(), s));
-            }
-        }
-        {
-            StageTimer t(idx, s, KNHIP_STAGE_TABLES); // (IVF_PQ: the filter's query operands / tables + the selectivity guard)
-            const bool want_i8 = kind == KNHIP_IVF_PQ && idx->pqf_form == 2;
-            if (kind == KNHIP_IVF_PQ) {
-                // Three forms of the filter (pq_filter.hip, pq_decode.hip).  DECODE form: rows decoded once per (list, <= 128
-                // queries), dense f16 contraction -- eps ~ 2^-9 B_q.  HALF tables: 8 queries per unit, eps = 2^-11 A_q: the
-                // tightest.  INT8 tables: 16 queries per unit, eps 8 .. 20 x the half form's (kept for KNHIP_PQF_FORM=int8).
-                // Selectivity guard: the sample dump predicts each query's candidate count under the eps of the half form and
-                // of the second form (decode, or int8 when asked for); the batch takes the second form when that count is
-                // small, else the half form, else -- data where even that lets a few percent of the rows through, so that the
-                // exact finish would cost more than the exact scan -- the exact 4-query kernel.
-                if (want_i8) { // (pass 1 -- ranges, midranges -- was part of the sample pass)
-                    HIP_TRY(launch_pqi_query_table(d_q, idx->cb.as<float4>(), d, nq, is_l2, idx->pabs_max, ws->ms_qi.p,
-                                                   ws->ms_qis.as<float>(), ws->ms_qmu.as<float>(), /*stats_done=*/true,
-                                                   s));
-                }
-                if (want_dec) { // the queries as halves + their error records (cheap: the guard reads the records; on the side
-                                // stream beside the sample pass it only shares the CUs with it: measured, no gain)
-                    if (int rc = ensure_pqd(idx)) return rc;
-                    HIP_TRY(ws->ms_qh16.reserve((size_t)nq * 128 * 2));
-                    HIP_TRY(ws->ms_qd.reserve((size_t)nq * 4 * sizeof(float)));
-                    HIP_TRY(launch_pqd_query_prep(d_q, idx->cb.as<float4>(), idx->pqd_st.as<float>(), nq, is_l2, idx->pabs_max,
-                                                  ws->ms_qh16.p, ws->ms_qd.as<float>(), s));
-                }
-                const bool want2 = want_i8 || want_dec;
-                const int form2 = want_dec ? 3 : 2;
-                const float* qs2 = want_dec ? ws->ms_qd.as<float>() : want_i8 ? ws->ms_qis.as<float>() : nullptr;
-                auto decide = [&](const int32_t* poor_h, int64_t n) -> int {
-                    if (want2 && (idx->pqf_form == form2 || (int64_t)poor_h[1] * 4 <= n)) {
-                        return form2;
-                    }
-                    if ((int64_t)poor_h[0] * 4 > n) {
-                        return 0;
-                    }
-                    return 1;
-                };
-                int form = want2 ? form2 : 1; // (guard off: the form asked for)
-                if (idx->pqf_guard) {
-                    int32_t* poor = ws->ms_cand_cnt.as<int32_t>() + 2 * nq + 1;
-                    // (the prediction pass -- 0.13 ms per 10^4 queries -- runs for the batches whose counters are looked at:
-                    // the synchronous ones and every fourth of the others)
-                    bool predicted = false;
-                    auto predict = [&]() -> hipError_t {
-                        if (predicted) {
-                            return hipSuccess;
-                        }
-                        predicted = true;
-                        return launch_pqf_predict(ws->dump.as<float>(), sample, ws->ms_nrow.as<int32_t>(), ws->gthr.as<float>(),
-                                                  ws->ms_qs.as<float>(), qs2, keys_p, nprobe, nlist,
-                                                  idx->d_list_len.as<int64_t>(), nq, ms_cap, k, is_l2, poor, s);
-                    };
-                    bool sync_now = true;
-                    // (at most 64 (k, nprobe) pairs are remembered -- an entry owns a pinned buffer and an event; a caller
-                    // that keeps inventing new pairs gets the synchronous decision)
-                    bool cached = false;
-                    {
-                        std::lock_guard<std::mutex> lk(idx->mu);
-                        cached = idx->guard_cache.size() < 64 || idx->guard_cache.count({k, nprobe}) != 0;
-                    }
-                    if (cached) {
-                        std::lock_guard<std::mutex> lk(idx->mu);
-                        knhip_index::GuardEntry& e = idx->guard_cache[{k, nprobe}];
-                        if (e.pending && hipEventQuery(e.ev) == hipSuccess) { // the previous batch's counters are in
-                            e.pending = false;
-                            e.form = decide(e.h_poor, e.pending_nq);
-                        }
-                        e.age++;
-                        const bool always_sync = env.guard_sync;
-                        if (e.form > 0 && !always_sync && (e.age & 63) != 0) {
-                            sync_now = false;
-                            form = e.form;
-                            if (!e.pending && (e.age & 3) == 0) {
-                                HIP_TRY(predict());
-                                if (e.h_poor == nullptr) {
-                                    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e.h_poor), 2 * sizeof(int32_t)));
-                                    HIP_TRY(hipEventCreateWithFlags(&e.ev, hipEventDisableTiming));
-                                }
-                                HIP_TRY(hipMemcpyAsync(e.h_poor, poor, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                                HIP_TRY(hipEventRecord(e.ev, s));
-                                e.pending = true;
-                                e.pending_nq = nq;
-                            }
-                        }
-                    }
-                    if (sync_now) {
-                        HIP_TRY(predict());
-                        int32_t h_poor[2] = {0, 0};
-                        HIP_TRY(hipMemcpyAsync(h_poor, poor, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                        HIP_TRY(hipStreamSynchronize(s));
-                        form = decide(h_poor, nq);
-                        if (cached) {
-                            std::lock_guard<std::mutex> lk(idx->mu);
-                            knhip_index::GuardEntry& e = idx->guard_cache[{k, nprobe}];
-                            if (!e.pending) {
-                                e.form = form;
-                            }
-                        }
-                    }
-                    if (form == 0) {
-                        return KNHIP_PQF_ABANDONED;
-                    }
-                }
-                pq_i8 = form == 2;
-                pq_dec = form == 3;
-                idx->last_pq_form = form;
-                if (form == 1) {
-                    // the queries' half tables + scales (the same records the sample pass wrote)
-                    if (int rc = ensure_pqf(idx)) return rc;
-                    m.pq_codes_r = idx->rows_r.as<uint4>();
-                    HIP_TRY(ws->ms_qh.reserve((size_t)nq * 256 * 32 * 2));
-                    HIP_TRY(launch_pqf_query_table(d_q, idx->cb.as<float4>(), d, nq, is_l2, idx->pabs_max, ws->ms_qh.p,
-                                                   ws->ms_qs.as<float>(), s));
-                    m.pq_qh = ws->ms_qh.p;
-                }
-                if (pq_i8) {
-                    if (int rc = ensure_pqi(idx)) return rc;
-                    qt = 16;
-                    HIP_TRY(ws->pq_recs16.reserve((size_t)std::max<int64_t>(std::max(units_bound, bound0), npairs) *
-                                                  sizeof(P16Rec)));
-                    m.pq_codes_r = idx->rows_r.as<uint4>();
-                    m.pq_codes_i = idx->rows_i.as<uint4>();
-                    m.pq_qi = ws->ms_qi.p;
-                    m.pq_qis = ws->ms_qis.as<float>();
-                    m.pq_recs16 = ws->pq_recs16.as<P16Rec>();
-                }
-                if (pq_dec) {
-                    qt = PD_QT;
-                    // units cut by cost (tiles x query tiles <= KNHIP_PQD_UNIT_COST): a long list probed by many queries
-                    // is several units, so no wave ends the launch alone on one, and a unit parks fewer records
-                    if (env.pqd_unit_cost > 0) {
-                        pqd_cost = env.pqd_unit_cost;
-                        pqd_bound = round_up(ms_units_cost_bound(npairs, PD_QT, nlist, idx->ntotal, idx->max_list_len,
-                                                                 pqd_cost), 8);
-                        HIP_TRY(ws->ms_units.reserve((size_t)pqd_bound * sizeof(KnItem)));
-                        HIP_TRY(ws->pqd_tiles.reserve((size_t)pqd_bound * sizeof(int2)));
-                        m.units = ws->ms_units.as<KnItem>(); // (the sample pass of IVF-PQ reads no units: nothing to keep)
-                        m.pq_unit_tiles = ws->pqd_tiles.as<int2>();
-                    }
-                    m.pq_cb16 = idx->pqd_cb16.p;
-                    m.pq_qh16 = ws->ms_qh16.p;
-                    m.pq_qd = ws->ms_qd.as<float>();
-                    m.pq_sc = idx->pqd_st.as<float>();
-                    m.pq_psum_s = idx->psum_s.as<float>();
-                    // where a wave parks passing lanes beyond its LDS region (192 records): a list that is the closest list of many
-                    // queries of the batch at once passes thousands of rows (C3: up to 3300 in one unit)
-                    m.pq_spill_cap = 4 * 8192; // (per workgroup: 8192 records per wave, 671 MB of scratch at 256 workgroups)
-                    if (idx->pqd_spill_cap > 0) {
-                        m.pq_spill_cap = idx->pqd_spill_cap;
-                    }
-                    m.pq_spill_wgs = 512;
-                    {
-                        int dev = 0, ncu = 0;
-                        (void)hipGetDevice(&dev);
-                        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) {
-                            m.pq_spill_wgs = ncu;
-                        }
-                    }
-                    HIP_TRY(ws->pq_spill.reserve((size_t)m.pq_spill_wgs * m.pq_spill_cap * 80));
-                    m.pq_spill = static_cast<unsigned char*>(ws->pq_spill.p);
-                }
-            }
-        }
-        {
-            // all probes of a list together: the work table again without the rank-0 split, its pairs cut into units
-            StageTimer t(idx, s, KNHIP_STAGE_GROUP);
-            WorkTable w2 = wside;
-            if (!wt1_lazy) {
-                w2.scan_bytes = reinterpret_cast<double*>(ws->ms_nunits.as<int64_t>() + 1); // (bytes were counted above)
-            }
-            if (wt2_done) {
-                if (int rc = sj.join()) return rc;
-            } else {
-                HIP_TRY(launch_build_worktable(keys_p, nq, nprobe, nlist, qg, qg, idx->d_list_len.as<int64_t>(),
-                                               idx->code_size, w2, s, /*rank0_slot=*/-1));
-            }
-            m.pairs = w2.pairs;
-            HIP_TRY(launch_ms_units(w2.list_count + nlist, w2.list_pair_off + nlist, nlist, qt,
-                                    ws->ms_unit_off.as<int64_t>(), ws->ms_nunits.as<int64_t>(),
-                                    ws->ms_units.as<KnItem>(), idx->d_list_len.as<int64_t>(), idx->code_size,
-                                    idx->scan_bytes_dev.as<double>() + 2, s, pqd_cost, ws->pqd_tiles.as<int2>()));
-        }
-        {
-            // phase 2: every (query, list) pair on the matrix cores
-            StageTimer t(idx, s, KNHIP_STAGE_SCAN);
-            HIP_TRY(launch_filter(m, std::max(units_bound, pqd_bound)));
-        }
-        {
-            // phase 3: exact distances of the candidates -> final top-k.  phase 4: overflowed queries.  First a RETRY
-            // (the exact k-th of the candidates a query gathered before it overflowed is a tight bound: its pairs are
-            // filtered once more as one-query units, then finished); whatever overflows again, or had no bound and no
-            // candidates, goes through the exact kernels (one-query items) and the ordinary merge.
-            StageTimer t(idx, s, KNHIP_STAGE_MERGE);
-            unsigned long long* counters = idx->coarse_fail_dev.as<unsigned long long>() + 1;
-            MScanArgs mf = m;
-            if (pq_i8) {
-                mf.pq_qs = m.pq_qis; // (the finish kernel's pruning reads eps_base at [q][2] of either)
-                mf.pq_prune_mu = 1;  // (... and the integer form's emission eps carries |sum of the per-m offsets|)
-            }
-            if (pq_dec) {
-                mf.pq_qs = m.pq_qd;  // (eps_base at [q][2], like the table forms' records)
-            }
-            HIP_TRY(launch_mscan_finish(mf, kind, is_l2, keys_p, cdis_p, nprobe, k, d_out_d, d_out_i, counters, 1, s));
-            HIP_TRY(launch_ms_flag_pairs(overflow, 2, keys_p, nq, nprobe, nlist, idx->d_list_len.as<int64_t>(), k,
-                                         ws->items.as<KnItem>(), wt.pairs, wt.nitems, nullptr, s));
-            MScanArgs r = m;
-            r.pairs = wt.pairs; // (ms_flag_pairs wrote the retried queries' one-pair units there)
-            r.units = ws->items.as<KnItem>();
-            r.nunits_dev = wt.nitems;
-            r.unit_loop = 1;
-            r.pq_unit_tiles = nullptr; // (the retry round's one-query units stay list-long)
-            r.ghist = nullptr; // (the retried rows were counted once already: counting them again would fake k candidates)
-            r.gmeta = nullptr;
-            HIP_TRY(launch_filter(r, npairs));
-            HIP_TRY(launch_mscan_finish(mf, kind, is_l2, keys_p, cdis_p, nprobe, k, d_out_d, d_out_i, counters, 2, s));
-            HIP_TRY(launch_ms_flag_pairs(overflow, 1, keys_p, nq, nprobe, nlist, idx->d_list_len.as<int64_t>(), k,
-                                         ws->items.as<KnItem>(), wt.pairs, wt.nitems, ws->partial_i.as<int64_t>(), s));
-            if (int rc = exact_one(ws->items.as<KnItem>(), wt.pairs, wt.nitems, std::min<int64_t>(npairs, 4096))) {
-                return rc;
-            }
-            HIP_TRY(launch_merge_partials(ws->partial_d.as<float>(), ws->partial_i.as<int64_t>(), nq, nprobe, k,
-                                          (int64_t)nprobe * k, k, is_l2, d_out_d, d_out_i, s, overflow));
-        }
-        return KNHIP_OK;
-    };
-
-    if (kind == KNHIP_IVF_FLAT) {
-        FlatScanArgs a{};
-        a.rows = idx->rows.as<float4>();
-        a.list_blk_off = idx->d_list_blk_off.as<int64_t>();
-        a.list_len = idx->d_list_len.as<int64_t>();
-        a.list_row_off = idx->d_list_row_off.as<int64_t>();
-        a.ids = idx->ids.as<int64_t>();
-        a.d = d;
-        a.nchunk = (d + 3) / 4;
-        a.queries = d_q;
-        a.nq = nq;
-        a.items = wt.items;
-        a.pairs = wt.pairs;
-        a.nitems_dev = wt.nitems;
-        a.bitset = d_bitset;
-        a.bitset_nbits = nbits;
-        a.partial_d = ws->partial_d.as<float>();
-        a.partial_i = ws->partial_i.as<int64_t>();
-        a.gthr = ws->gthr.as<float>();
-        a.nslot = nprobe;
-        a.k = k;
-        a.row_scale = idx->row_scale.as<float>();
-        a.cos_mode = idx->cos_mode;
-        if (use_ms) {
-            return run_mscan([&](const KnItem* items, const KnPair* pairs, const int64_t* nitems, int64_t grid) -> int {
-                FlatScanArgs b = a;
-                b.items = items;
-                b.pairs = pairs;
-                b.nitems_dev = nitems;
-                b.item_loop = 1;
-                HIP_TRY(launch_flat_scan(b, is_l2, false, grid, s, /*qg_override=*/1));
-                return KNHIP_OK;
-            });
-        }
-        StageTimer t(idx, s, KNHIP_STAGE_SCAN);
-        HIP_TRY(launch_flat_scan(a, is_l2, false, items_bound, s));
-    } else if (kind == KNHIP_IVF_PQ) {
-        const int M = idx->desc.pq_m;
-        const int mode = !is_l2 ? PQ_LUT_IP : (idx->use_precomp ? PQ_LUT_PRECOMP : PQ_LUT_RESIDUAL);
-        if (mode != PQ_LUT_RESIDUAL && !(pq_use_q4 && !pq_rank0)) { // (pq_scan_q4 computes its tables from the codebook)
-            HIP_TRY(ws->t2t.reserve((size_t)nq * 256 * M * sizeof(float)));
-            StageTimer t(idx, s, KNHIP_STAGE_LUT);
-            HIP_TRY(launch_pq_query_table(d_q, idx->cb.as<float>(), d, M, nq, ws->t2t.as<float>(), s));
-        }
-        PqScanArgs a{};
-        a.codes_skew = idx->rows.as<uint4>();
-        a.list_sblk_off = idx->d_list_blk_off.as<int64_t>();
-        a.list_len = idx->d_list_len.as<int64_t>();
-        a.list_row_off = idx->d_list_row_off.as<int64_t>();
-        a.ids = idx->ids.as<int64_t>();
-        a.precomp_t = idx->precomp_t.as<float>();
-        a.cb = idx->cb.as<float>();
-        a.centroids = idx->centroids.as<float>();
-        a.d = d;
-        a.lut_mode = mode;
-        a.queries = d_q;
-        a.t2t = ws->t2t.as<float>();
-        a.coarse_dis = cdis_p;
-        a.items = wt.items;
-        a.pairs = wt.pairs;
-        a.nitems_dev = wt.nitems;
-        a.bitset = d_bitset;
-        a.bitset_nbits = nbits;
-        a.partial_d = ws->partial_d.as<float>();
-        a.partial_i = ws->partial_i.as<int64_t>();
-        a.gthr = ws->gthr.as<float>();
-        a.nslot = nprobe;
-        a.k = k;
-        if (use_ms) {
-            // half-precision prefilter + exact finish (pq_filter.hip); the queries that overflow twice take the exact
-            // 4-query kernel over one-pair items
-            if (pq_q4_ok) {
-                a.codes_skew = idx->rows2.as<uint4>();
-                a.list_sblk_off = idx->d_list_blk_off2.as<int64_t>();
-                a.cb_t = idx->cb_t.as<float4>();
-            }
-            const int rc_ms = run_mscan([&](const KnItem* items, const KnPair* pairs, const int64_t* nitems, int64_t) -> int {
-                PqScanArgs b = a;
-                b.items = items;
-                b.pairs = pairs;
-                b.nitems_dev = nitems;
-                b.item_lo = nullptr;
-                b.item_hi = nitems;
-                if (!pq_q4_ok) {
-                    // k > 128: the systolic kernel, one workgroup per one-pair item (normally none: the workgroups of
-                    // the launch read the item count and return)
-                    if (!idx->skew_ready) {
-                        if (int rc = build_pq_skew(idx)) return rc;
-                    }
-                    b.codes_skew = idx->rows.as<uint4>();
-                    b.list_sblk_off = idx->d_list_blk_off.as<int64_t>();
-                    HIP_TRY(launch_pq_scan(b, is_l2, M, npairs, s));
-                    return KNHIP_OK;
-                }
-                HIP_TRY(ws->recs4.reserve((size_t)npairs * sizeof(P4Rec)));
-                HIP_TRY(ws->q4_ctr.reserve(8 * 16 * sizeof(int32_t)));
-                b.recs4 = ws->recs4.as<P4Rec>();
-                b.q4_ctr = ws->q4_ctr.as<int32_t>();
-                HIP_TRY(launch_pq_scan_q4(b, is_l2, npairs, s));
-                return KNHIP_OK;
-            });
-            if (rc_ms != KNHIP_PQF_ABANDONED) {
-                return rc_ms;
-            }
-            if (int rc = build_wt1()) return rc;
-            // (the guard found the batch poorly selective: the exact 4-query kernel over the work table built above -- both
-            // classes of the sample split are ordinary items of 4 pairs; gthr holds the sample's bounds, which are valid)
-        }
-        if (pq_use_v2) {
-            a.codes_skew = idx->rows2.as<uint4>();
-            a.list_sblk_off = idx->d_list_blk_off2.as<int64_t>();
-            a.item_hi = wt.nitems;
-            const int64_t stride = round_up(std::max<int64_t>(idx->max_list_len, 64), 64);
-            if (pq_rank0) {
-                // phase A: the rank-0 probe of every query (work items of virtual lists [0, nlist) come
-                // first: worktable.hip) in dump mode, then radix select -> partial slot 0 + thresholds
-                HIP_TRY(ws->dump.reserve((size_t)nq * stride * sizeof(float)));
-                HIP_TRY(ws->sel_keys.reserve((size_t)nq * k * sizeof(int64_t)));
-                HIP_TRY(ws->sel_d.reserve((size_t)nq * k * sizeof(float)));
-                HIP_TRY(ws->ghist.reserve((size_t)nq * 64 * sizeof(uint32_t)));
-                HIP_TRY(ws->gmeta.reserve((size_t)nq * sizeof(uint2)));
-                a.dump = ws->dump.as<float>();
-                a.dump_stride = stride;
-                a.item_lo = nullptr;
-                a.item_hi = wt.list_item_off + nlist; // items of the rank-0 virtual lists
-                const int64_t boundA = round_up(nq / qg_rank0 + std::min<int64_t>(nlist, nq) + 1, 8);
-                {
-                    StageTimer t(idx, s, KNHIP_STAGE_SCAN_RANK0);
-                    HIP_TRY(launch_pq_scan_v2(a, is_l2, true, boundA, s));
-                    HIP_TRY(launch_rank0_select(a.dump, stride, keys_p, nprobe,
-                                                idx->d_list_len.as<int64_t>(), idx->d_list_row_off.as<int64_t>(),
-                                                idx->ids.as<int64_t>(), nq, k, is_l2, a.partial_d, a.partial_i,
-                                                a.gthr, ws->sel_keys.as<int64_t>(), ws->sel_d.as<float>(),
-                                                idx->cand_hist ? ws->ghist.as<uint32_t>() : nullptr,
-                                                ws->gmeta.as<uint2>(), s));
-                }
-                if (idx->cand_hist) {
-                    a.ghist = ws->ghist.as<uint32_t>();
-                    a.gmeta = ws->gmeta.as<uint2>();
-                }
-                idx->rank0_phase_used = true;
-                // phase B: every other probe
-                a.item_lo = wt.list_item_off + nlist;
-                a.item_hi = wt.nitems;
-            } else {
-                idx->rank0_phase_used = false;
-            }
-            StageTimer t(idx, s, KNHIP_STAGE_SCAN);
-            if (pq_use_q4) {
-                HIP_TRY(ws->recs4.reserve((size_t)items_bound * sizeof(P4Rec)));
-                HIP_TRY(ws->q4_ctr.reserve(8 * 16 * sizeof(int32_t)));
-                a.recs4 = ws->recs4.as<P4Rec>();
-                a.q4_ctr = ws->q4_ctr.as<int32_t>();
-                a.cb_t = idx->cb_t.as<float4>();
-                HIP_TRY(launch_pq_scan_q4(a, is_l2, items_bound, s));
-            } else {
-                HIP_TRY(launch_pq_scan_v2(a, is_l2, false, items_bound, s));
-            }
-        } else {
-            idx->rank0_phase_used = false;
-            if (!idx->skew_ready) {
-                if (int rc = build_pq_skew(idx)) return rc;
-                a.codes_skew = idx->rows.as<uint4>();
-            }
-            StageTimer t(idx, s, KNHIP_STAGE_SCAN);
-            HIP_TRY(launch_pq_scan(a, is_l2, M, items_bound, s));
-        }
-    } else { // IVF_SQ8
-        SqScanArgs a{};
-        a.rows = idx->rows.as<uint4>();
-        a.list_blk_off = idx->d_list_blk_off.as<int64_t>();
-        a.list_len = idx->d_list_len.as<int64_t>();
-        a.list_row_off = idx->d_list_row_off.as<int64_t>();
-        a.ids = idx->ids.as<int64_t>();
-        a.trained = idx->sq_trained.as<float>();
-        a.centroids = idx->centroids.as<float>();
-        a.d = d;
-        a.nchunk16 = sq_nchunk16(d, idx->sq_bits);
-        a.bits = idx->sq_bits;
-        a.queries = d_q;
-        a.coarse_dis = cdis_p;
-        a.items = wt.items;
-        a.pairs = wt.pairs;
-        a.nitems_dev = wt.nitems;
-        a.bitset = d_bitset;
-        a.bitset_nbits = nbits;
-        a.partial_d = ws->partial_d.as<float>();
-        a.partial_i = ws->partial_i.as<int64_t>();
-        a.gthr = ws->gthr.as<float>();
-        a.nslot = nprobe;
-        a.k = k;
-        if (use_ms) {
-            return run_mscan([&](const KnItem* items, const KnPair* pairs, const int64_t* nitems, int64_t grid) -> int {
-                SqScanArgs b = a;
-                b.items = items;
-                b.pairs = pairs;
-                b.nitems_dev = nitems;
-                b.item_loop = 1;
-                HIP_TRY(launch_sq_scan(b, is_l2, grid, s, /*qg_override=*/1));
-                return KNHIP_OK;
-            });
-        }
-        StageTimer t(idx, s, KNHIP_STAGE_SCAN);
-        HIP_TRY(launch_sq_scan(a, is_l2, items_bound, s));
-    }
-    {
-        StageTimer t(idx, s, KNHIP_STAGE_MERGE);
-        HIP_TRY(launch_merge_partials(ws->partial_d.as<float>(), ws->partial_i.as<int64_t>(), nq, nprobe, k,
-                                      (int64_t)nprobe * k, k, is_l2, d_out_d, d_out_i, s));
-    }
-    return KNHIP_OK;
-}
-
-int validate_search(const knhip_index* idx, int64_t nq, int32_t k, int32_t& nprobe) {
-    if (nq < 0 || k <= 0) {
-        return fail(KNHIP_ERR_INVALID_ARGS, "nq must be >= 0 and k > 0");
-    }
-    if (k > KNHIP_MAX_K) { // (1024 < k <= 16384: the large-k path, knhip_api_range.hip)
-        return fail(KNHIP_ERR_INVALID_ARGS, "k > 16384 is not supported");
-    }
-    const int kind = idx->desc.kind;
-    if (kind == KNHIP_BRUTE_FORCE) {
-        if (!idx->has_data) {
-            return fail(KNHIP_ERR_EMPTY_INDEX, "brute-force index holds no vectors");
-        }
-        return KNHIP_OK;
-    }
-    if (!idx->has_coarse) {
-        return fail(KNHIP_ERR_NOT_TRAINED, "coarse centroids not set");
-    }
-    if (kind == KNHIP_IVF_PQ && !idx->has_pq) {
-        return fail(KNHIP_ERR_NOT_TRAINED, "PQ codebooks not set");
-    }
-    if (kind == KNHIP_IVF_SQ8 && !idx->has_sq) {
-        return fail(KNHIP_ERR_NOT_TRAINED, "SQ parameters not set");
-    }
-    if (!idx->has_data) {
-        return fail(KNHIP_ERR_EMPTY_INDEX, "inverted lists not set");
-    }
-    if (nprobe <= 0) {
-        return fail(KNHIP_ERR_INVALID_ARGS, "nprobe must be > 0");
-    }
-    if (nprobe > idx->nlist) {
-        nprobe = (int32_t)idx->nlist; // IndexIVF.cpp:321-322
-    }
-    if ((size_t)nprobe > row_select_max_k()) {
-        return fail(KNHIP_ERR_NOT_IMPLEMENTED, "nprobe > 65536 is not supported");
-    }
-    return KNHIP_OK;
-}
-
-// how many queries per batch so the scratch stays within ~8 GiB
-int64_t query_batch(const knhip_index* idx, int64_t nq, int k, int nprobe) {
-    double per_q;
-    if (idx->desc.kind == KNHIP_BRUTE_FORCE) {
-        const int64_t nb = idx->ntotal;
-        int64_t chunk_rows = std::max<int64_t>(1024, round_up((nb + 511) / 512, 64));
-        const int64_t nchunks = (nb + chunk_rows - 1) / chunk_rows;
-        per_q = (double)nchunks * k * 12.0;
-    } else {
-        per_q = (double)idx->nlist * 4.0 + (double)nprobe * (12.0 + 8.0 + (double)k * 12.0);
-        if ((size_t)nprobe > row_select_lds_max_k()) {
-            per_q += 16.0 * nprobe; // sort scratch of the row selection (next power of two of nprobe, 8 bytes each)
-        }
-        if ((idx->desc.kind == KNHIP_IVF_FLAT || idx->desc.kind == KNHIP_IVF_SQ8) && idx->mscan != 0) {
-            per_q += 4.0 * mscan_sample_rows() + 8.0 * 32768.0; // sample dump + candidate list (mfma_scan.hip)
-        }
-        if (idx->desc.kind == KNHIP_IVF_PQ && idx->pqf != 0) {
-            // sample dump + candidate list + half table + one-pair records of the fallbacks (pq_filter.hip)
-            per_q += 4.0 * mscan_sample_rows() + 12.0 * 32768.0 + 16384.0 + 8192.0 + (double)nprobe * (256.0 + 96.0);
-        }
-        if (idx->desc.kind == KNHIP_IVF_PQ) {
-            per_q += 256.0 * idx->desc.pq_m * 4.0;
-            if (!pq_scan_supported_m(idx->desc.pq_m)) { // (pq_scan_any.hip: four partial lists per probe)
-                per_q += (double)nprobe * (pq_scan_any_parts(k) - 1) * (double)k * 12.0;
-            }
-        }
-    }
-    const double budget = 8.0 * 1024 * 1024 * 1024;
-    int64_t qb = (int64_t)(budget / std::max(per_q, 1.0));
-    qb = std::max<int64_t>(qb, 8);
-    qb = std::min<int64_t>(qb, 65536 * 16);
-    return std::min(qb, std::max<int64_t>(nq, 1));
+// what knhip_profile_get reports of the last search
+void note_route(const knhip_index* idx, bool bf_mfma, int pq_form, bool rank0_phase, int64_t items_bound) {
+    std::lock_guard<std::mutex> lk(idx->mu);
+    idx->last_bf_mfma = bf_mfma ? 1 : 0;
+    idx->last_pq_form = pq_form;
+    idx->rank0_phase_used = rank0_phase;
+    idx->last_items_bound = items_bound;
 }
 
 } // namespace knhip_host

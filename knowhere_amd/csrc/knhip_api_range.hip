@@ -91,8 +91,6 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
         const int64_t npairs = nq * W;
         if (kind == KNHIP_IVF_PQ && !(idx->pq_v2 && idx->desc.pq_m == 32)) {
             // code widths without a dump mode in the fast ADC kernels: the plain exact ADC kernel of range.hip
-            const int M = idx->desc.pq_m;
-            const int mode = !is_l2 ? PQ_LUT_IP : (idx->use_precomp ? PQ_LUT_PRECOMP : PQ_LUT_RESIDUAL);
             PqDumpArgs a{};
             a.dist = ws->dump.as<float>();
             a.ncol = ncol;
@@ -104,9 +102,9 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
             a.list_len = idx->d_list_len.as<int64_t>();
             a.list_row_off = idx->d_list_row_off.as<int64_t>();
             a.codes = idx->codes_aos.as<uint8_t>();
-            a.M = M;
+            a.M = idx->desc.pq_m;
             a.d = d;
-            a.lut_mode = mode;
+            a.lut_mode = pq_lut_mode(idx);
             a.t2t = ws->t2t.as<float>();
             a.precomp_t = idx->precomp_t.as<float>();
             a.cb = idx->cb.as<float>();
@@ -117,54 +115,24 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
         }
         const int qg = kind == KNHIP_IVF_PQ ? pq_scan_qg(idx->desc.pq_m) : 8;
         const int64_t items_bound = round_up(npairs / qg + std::min<int64_t>(2 * nlist, npairs) + 1, 8);
-        HIP_TRY(ws->list_count.reserve((size_t)2 * nlist * sizeof(int32_t)));
-        HIP_TRY(ws->list_cursor.reserve((size_t)2 * nlist * sizeof(int32_t)));
-        HIP_TRY(ws->list_pair_off.reserve((size_t)(2 * nlist + 1) * sizeof(int64_t)));
-        HIP_TRY(ws->list_item_off.reserve((size_t)(2 * nlist + 1) * sizeof(int64_t)));
-        HIP_TRY(ws->pairs.reserve((size_t)npairs * sizeof(KnPair)));
-        HIP_TRY(ws->items.reserve((size_t)items_bound * sizeof(KnItem)));
-        HIP_TRY(ws->nitems.reserve(sizeof(int64_t)));
+        HIP_TRY(ws->wt[0].reserve(nlist, npairs, items_bound));
         HIP_TRY(ws->gthr.reserve((size_t)nq * sizeof(float)));
         HIP_TRY(launch_fill_f32(ws->gthr.as<float>(), nq, is_l2 ? FLT_MAX : -FLT_MAX, s));
-        WorkTable wt{};
-        wt.list_count = ws->list_count.as<int32_t>();
-        wt.list_cursor = ws->list_cursor.as<int32_t>();
-        wt.list_pair_off = ws->list_pair_off.as<int64_t>();
-        wt.list_item_off = ws->list_item_off.as<int64_t>();
-        wt.pairs = ws->pairs.as<KnPair>();
-        wt.items = ws->items.as<KnItem>();
-        wt.nitems = ws->nitems.as<int64_t>();
-        wt.scan_bytes = idx->scan_bytes_dev.as<double>();
+        const WorkTable wt = ws->wt[0].bind(idx->scan_bytes_dev.as<double>());
         if (npairs <= 2048 && npairs <= items_bound) {
             // (one or two queries -- the boundary rule's flagged ones --: one item per pair instead of the grouped table)
             HIP_TRY(launch_direct_items(keys_w, nq, W, nlist, idx->d_list_len.as<int64_t>(), wt, s));
         } else {
             HIP_TRY(launch_build_worktable(keys_w, nq, W, nlist, qg, qg, idx->d_list_len.as<int64_t>(), idx->code_size, wt, s));
         }
+        // (dump mode: k = 1, no partial lists)
+        const Batch in{d_q, nq, 1, W, d_bitset, nbits, nullptr, nullptr, keys_w, cdis_w};
         if (kind == KNHIP_IVF_PQ) {
-            const int mode = !is_l2 ? PQ_LUT_IP : (idx->use_precomp ? PQ_LUT_PRECOMP : PQ_LUT_RESIDUAL);
-            PqScanArgs a{};
+            PqScanArgs a = pq_scan_args(idx, ws, in, wt);
             a.codes_skew = idx->rows2.as<uint4>();
             a.list_sblk_off = idx->d_list_blk_off2.as<int64_t>();
-            a.list_len = idx->d_list_len.as<int64_t>();
-            a.list_row_off = idx->d_list_row_off.as<int64_t>();
-            a.ids = idx->ids.as<int64_t>();
-            a.precomp_t = idx->precomp_t.as<float>();
-            a.cb = idx->cb.as<float>();
-            a.centroids = idx->centroids.as<float>();
-            a.d = d;
-            a.lut_mode = mode;
-            a.queries = d_q;
-            a.t2t = ws->t2t.as<float>();
-            a.coarse_dis = cdis_w;
-            a.items = wt.items;
-            a.pairs = wt.pairs;
-            a.nitems_dev = wt.nitems;
-            a.bitset = d_bitset;
-            a.bitset_nbits = nbits;
-            a.gthr = ws->gthr.as<float>();
-            a.nslot = W;
-            a.k = 1;
+            a.partial_d = nullptr;
+            a.partial_i = nullptr;
             a.item_lo = nullptr;
             a.item_hi = wt.nitems;
             a.dump = ws->dump.as<float>();
@@ -173,27 +141,9 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
             a.dump_pair_col = pair_col;
             HIP_TRY(launch_pq_scan_v2(a, is_l2, true, items_bound, s));
         } else {
-            SqScanArgs a{};
-            a.rows = idx->rows.as<uint4>();
-            a.list_blk_off = idx->d_list_blk_off.as<int64_t>();
-            a.list_len = idx->d_list_len.as<int64_t>();
-            a.list_row_off = idx->d_list_row_off.as<int64_t>();
-            a.ids = idx->ids.as<int64_t>();
-            a.trained = idx->sq_trained.as<float>();
-            a.centroids = idx->centroids.as<float>();
-            a.d = d;
-            a.nchunk16 = sq_nchunk16(d, idx->sq_bits);
-            a.bits = idx->sq_bits;
-            a.queries = d_q;
-            a.coarse_dis = cdis_w;
-            a.items = wt.items;
-            a.pairs = wt.pairs;
-            a.nitems_dev = wt.nitems;
-            a.bitset = d_bitset;
-            a.bitset_nbits = nbits;
-            a.gthr = ws->gthr.as<float>();
-            a.nslot = W;
-            a.k = 1;
+            SqScanArgs a = sq_scan_args(idx, ws, in, wt);
+            a.partial_d = nullptr;
+            a.partial_i = nullptr;
             a.dump = ws->dump.as<float>();
             a.dump_stride = ncol;
             a.dump_pair_col = pair_col;
@@ -204,7 +154,7 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
     HIP_TRY(ws->rg_cnt.reserve((size_t)nq * nprobe * sizeof(int32_t)));
     if (kind == KNHIP_IVF_PQ) {
         const int M = idx->desc.pq_m;
-        const int mode = !is_l2 ? PQ_LUT_IP : (idx->use_precomp ? PQ_LUT_PRECOMP : PQ_LUT_RESIDUAL);
+        const int mode = pq_lut_mode(idx);
         if (mode != PQ_LUT_RESIDUAL) {
             HIP_TRY(ws->t2t.reserve((size_t)nq * 256 * M * sizeof(float)));
             HIP_TRY(launch_pq_query_table(d_q, idx->cb.as<float>(), d, M, nq, ws->t2t.as<float>(), s));

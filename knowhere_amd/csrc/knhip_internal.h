@@ -10,7 +10,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -90,6 +89,29 @@ struct DeviceGuard {
     }
 };
 
+// the buffers of one work table (worktable.hip: the (query, probe) pairs of a batch grouped into per-list work items)
+struct WorkTableBufs {
+    DevBuf list_count, list_pair_off, list_item_off, list_cursor, pairs, items, nitems;
+    hipError_t reserve(int64_t nlist, int64_t npairs, int64_t nitems_max) {
+        const size_t nl = (size_t)2 * nlist;
+        const std::pair<DevBuf*, size_t> want[] = {
+                {&list_count, nl * sizeof(int32_t)},          {&list_cursor, nl * sizeof(int32_t)},
+                {&list_pair_off, (nl + 1) * sizeof(int64_t)}, {&list_item_off, (nl + 1) * sizeof(int64_t)},
+                {&pairs, (size_t)npairs * sizeof(KnPair)},    {&items, (size_t)nitems_max * sizeof(KnItem)},
+                {&nitems, sizeof(int64_t)}};
+        for (const auto& w : want) {
+            if (hipError_t e = w.first->reserve(w.second); e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    // the kernels' view of the buffers (empty_mark: where empty lists are marked, see WorkTable)
+    WorkTable bind(double* scan_bytes, int64_t* empty_mark = nullptr, int k = 0) const {
+        return WorkTable{list_count.as<int32_t>(), list_pair_off.as<int64_t>(), list_item_off.as<int64_t>(), list_cursor.as<int32_t>(),
+                         pairs.as<KnPair>(),       items.as<KnItem>(),          nitems.as<int64_t>(),        scan_bytes,
+                         empty_mark,               k};
+    }
+};
+
 // per-stream scratch; stream order makes reuse by consecutive searches on one stream safe
 struct Workspace {
     DevBuf coarse_full;  // [qb][nlist] exact distances
@@ -113,9 +135,9 @@ struct Workspace {
     DevBuf q4_ctr;       // [8 * 16] per-XCD item counters
     DevBuf ghist;        // [qb][64] per-query candidate histogram (pq_scan_v2 after a rank-0 phase)
     DevBuf gmeta;        // [qb] {first-bin key, shift}
-    DevBuf list_count, list_pair_off, list_item_off, list_cursor, pairs, items, nitems;
-    // a second work table (row-kind prefilters: the all-probes table is built on the side stream beside the sample pass)
-    DevBuf list_count2, list_pair_off2, list_item_off2, list_cursor2, pairs2, items2, nitems2;
+    // [0]: the search's work table; [1]: a second one (row-kind prefilters: the all-probes table is built on the side stream
+    // beside the sample pass)
+    WorkTableBufs wt[2];
     // MFMA prefilter of the IVF-Flat / IVF-SQ8 scans (mfma_scan.hip)
     DevBuf ms_qi, ms_qis, ms_qmu, pq_recs16;                                 // integer form: tables, {step, mu sum, eps, A}, records
     DevBuf rs_ovf;                                                    // coarse stage: rows the two-pass selection left to the radix select
@@ -274,7 +296,7 @@ struct knhip_index {
     mutable bool idmap_ready = false; // IVF-Flat direct map (knhip_index_get_vectors): built on first use
     mutable DevBuf idmap_ids, idmap_col;
     mutable int64_t last_range_ranks = 0; // coarse ranks the last range search scanned per query (rank waves)
-    mutable int last_pq_form = 0;    // prefilter form of the last search: 0 none (exact kernels), 1 half precision, 2 int8
+    mutable int last_pq_form = 0;    // prefilter form of the last search: 0 none (exact kernels), 1 half precision, 2 int8, 3 decode
     mutable DevBuf rows_i;           // token stream of the integer form (stream16i)
     mutable DevBuf rows_r;           // rotated token stream (stream16r)
     mutable DevBuf d_list_blk_off_r; // [nlist + 1]
@@ -362,12 +384,60 @@ int build_list_layout(knhip_index* idx, const std::vector<int64_t>& list_off, co
 int ensure_aos(const knhip_index* cidx);
 Workspace* acquire_ws(const knhip_index* idx, void* stream_key, bool pooled_by_stream);
 void release_ws(const knhip_index* idx, Workspace* w);
-// one batch of queries, everything on the device (pre_keys / pre_cdis non-null: the coarse assignment is given)
+// (knhip_api_search.hip) one batch of queries, all on the device (pre_keys / pre_cdis non-null: the coarse assignment is given)
 int search_batch(const knhip_index* idx, Workspace* ws, const float* d_q, int64_t nq, int k, int nprobe, const uint8_t* d_bitset,
                  int64_t nbits, int64_t* d_out_i, float* d_out_d, hipStream_t s, const int64_t* pre_keys = nullptr,
                  const float* pre_cdis = nullptr);
 int validate_search(const knhip_index* idx, int64_t nq, int32_t k, int32_t& nprobe);
 int64_t query_batch(const knhip_index* idx, int64_t nq, int k, int nprobe);
+// ---- what knhip_api_search.hip takes from knhip_api.hip: the "nearest rows of every query" stage, layouts built on first use
+// the rows the stage runs over: the coarse quantizer's centroids, or a chunk of a BRUTE_FORCE base
+struct CoarseRows {
+    const float* rows;      // [n][d] row major
+    const float4* rows_il;  // interleaved 64-row blocks
+    const void* rows_bs;    // split bf16 operand rows (null: the bf16 prefilter is not available)
+    const float* norm;      // [n] ||x||^2
+    float norm_max;
+    int64_t n;
+};
+// a search over several row sets one after the other (the chunks of a BRUTE_FORCE base): the k-th best distance found so far
+// bounds what a later chunk can contribute, so only the FIRST chunk needs the two-pass form (group minima -> bound ->
+// candidates); the others take the running k-th, widened by the prefilter's eps, as their selection bound and make ONE pass
+struct RowsRun {
+    float* kth;          // [nq] running k-th best exact distance (worst value before the first chunk)
+    bool have_bound;     // a chunk has been searched: kth bounds this one
+    bool queries_ready;  // the queries' norms and split operand rows of this batch are in the workspace already
+};
+int coarse_rows_stage(const knhip_index* idx, Workspace* ws, const CoarseRows& R, const float* d_q, int64_t nq, int nprobe,
+                      int64_t* keys, float* cdis, hipStream_t s, RowsRun* run = nullptr);
+int build_pq_skew(const knhip_index* cidx);
+int ensure_mscan_norms(const knhip_index* idx);
+int ensure_psum(const knhip_index* idx);
+int ensure_pqf(const knhip_index* idx);
+int ensure_pqd(const knhip_index* idx);
+int ensure_pqi(const knhip_index* idx);
+int ensure_bf_split(const knhip_index* idx);
+// what knhip_profile_get reports of the last search (under idx->mu): matrix-core BRUTE_FORCE, prefilter form, rank-0 phase, items
+void note_route(const knhip_index* idx, bool bf_mfma, int pq_form, bool rank0_phase, int64_t items_bound);
+// one batch of queries (device pointers), its coarse assignment [nq][nprobe] and where its results go
+struct Batch {
+    const float* q;
+    int64_t nq;
+    int k, nprobe;
+    const uint8_t* bitset;
+    int64_t nbits;
+    int64_t* out_i;
+    float* out_d;
+    const int64_t* keys;
+    const float* cdis;
+};
+// (knhip_api_search.hip; range search too) the scan kernels' arguments; the callers set dump mode, item range, item_loop, layout 2
+FlatScanArgs flat_scan_args(const knhip_index* idx, const Workspace* ws, const Batch& b, const WorkTable& wt);
+SqScanArgs sq_scan_args(const knhip_index* idx, const Workspace* ws, const Batch& b, const WorkTable& wt);
+PqScanArgs pq_scan_args(const knhip_index* idx, const Workspace* ws, const Batch& b, const WorkTable& wt);
+PqAnyArgs pq_any_args(const knhip_index* idx, const Workspace* ws, const Batch& b);
+inline int pq_lut_mode(const knhip_index* x) { return !x->is_l2 ? PQ_LUT_IP : (x->use_precomp ? PQ_LUT_PRECOMP : PQ_LUT_RESIDUAL); }
+inline int64_t bf_chunk_rows(int64_t nb) { return std::max<int64_t>(1024, round_up((nb + 511) / 512, 64)); } // (BRUTE_FORCE row scan)
 // search_batch + the reference's first-come admission at the k-th boundary (knhip_api_range.hip)
 int search_batch_ties(const knhip_index* idx, Workspace* ws, const float* d_q, int64_t nq, int k, int nprobe,
                       const uint8_t* d_bitset, int64_t nbits, int64_t* d_out_i, float* d_out_d, hipStream_t s,

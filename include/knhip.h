@@ -73,6 +73,7 @@ extern "C" {
  * pq_nbits 1 .. 8 (host-side list codes in the reference's bit-string form).
  * Additive since 9 (new functions only, no structure touched, the version stays 9): the AnnIterator, knhip_iter_*.
  * Additive since 9: KNHIP_MAX_K, knhip_select_ordered_device (search and refine with 1024 < k <= 16384).
+ * Additive since 9: knhip_index_set_row_type / knhip_index_get_row_type (IVF_FLAT rows kept as fp16 / bf16 in HBM).
  * Callers compare knhip_abi_version() with the header they were built against. */
 #define KNHIP_ABI_VERSION 9
 /* Largest k of a search and largest k_base of a refine (additive since 9: the large-k path, knhip_select_ordered_device). */
@@ -152,6 +153,24 @@ int knhip_index_set_sq(knhip_index* idx, const float* vmin, const float* vdiff);
  * codes only.  knhip_index_get_sq_type returns the width, or 0 for an index of another kind. */
 int knhip_index_set_sq_type(knhip_index* idx, int32_t bits);
 int32_t knhip_index_get_sq_type(const knhip_index* idx);
+/* IVF_FLAT: the element type the list rows are KEPT in on the device.  Additive to ABI 9.  Settable only on a KNHIP_IVF_FLAT
+ * index that holds no rows yet; KNHIP_ERR_INVALID_ARGS for another value, another kind, or an index with rows; setting
+ * KNHIP_ROWTYPE_FP32 is always allowed and changes nothing.  Only the layout in HBM changes: every entry point that takes or
+ * returns rows keeps fp32 at its boundary (knhip_index_add_lists / _add / _add_device / _add_assigned_by /
+ * _set_lists_device / _get_lists / _get_vectors / _find_vectors), host-side list codes stay the reference's IndexIVFFlat
+ * bytes and code_size stays 4 dim; every Add narrows on the device and every resident copy of the rows (64-row blocks of
+ * 16-byte chunks of 8 dimensions, zero padded; the AoS copy short lists keep) is narrow, so knhip_index_device_bytes
+ * shrinks.  A value is accepted only if narrowing and widening give back its 32 bits:
+ *   bf16: the low 16 bits of the fp32 pattern are zero and the value is no NaN (subnormals included: integer logic only);
+ *   fp16: +-0, every fp16 normal and subnormal (magnitudes 2^-24 .. 65504), +-inf; no NaN.
+ * A batch with any other value fails with KNHIP_ERR_INVALID_ARGS before anything is merged -- knhip_last_error names the
+ * type and the first offending (row, dimension), the index stays as it was; nothing is ever rounded.  The kernels widen in
+ * registers (exact) and run the fp32 arithmetic, so every search, range search, iterator, tie pass, refine first stage and
+ * stored-norm cosine returns what the fp32 index returns for the same rows, bit for bit.  Out of scope: BRUTE_FORCE,
+ * int8 rows, shard groups, a typed host boundary.  knhip_index_get_row_type: 0 for fp32 and for every other kind. */
+enum { KNHIP_ROWTYPE_FP32 = 0, KNHIP_ROWTYPE_FP16 = 1, KNHIP_ROWTYPE_BF16 = 2 };
+int knhip_index_set_row_type(knhip_index* idx, int32_t row_type);
+int32_t knhip_index_get_row_type(const knhip_index* idx);
 /* COSINE with stored norms, as the CPU nodes keep it for FLAT and IVF_FLAT: raw rows + one float per row, applied to the
  * finished inner product of every scanned row (Search and RangeSearch):
  *   mode 1: dis = <q, y> / scale      IVFFlatScanner with code norms (cppcontrib/knowhere/IndexIVFFlat.cpp:199-210),

@@ -41,7 +41,7 @@ class StageTimes(C.Structure):
 # every symbol include/knhip.h declares (tests check the .so exports all of them)
 SYMBOLS = [
     "knhip_abi_version", "knhip_device_count", "knhip_last_error", "knhip_index_create",
-    "knhip_index_destroy", "knhip_index_set_coarse", "knhip_index_set_pq", "knhip_index_set_sq", "knhip_index_set_sq_type", "knhip_index_get_sq_type", "knhip_index_set_row_scale", "knhip_index_add_assigned_by", "knhip_index_get_desc",
+    "knhip_index_destroy", "knhip_index_set_coarse", "knhip_index_set_pq", "knhip_index_set_sq", "knhip_index_set_sq_type", "knhip_index_get_sq_type", "knhip_index_set_row_type", "knhip_index_get_row_type", "knhip_index_set_row_scale", "knhip_index_add_assigned_by", "knhip_index_get_desc",
     "knhip_index_add_lists", "knhip_index_add_vectors", "knhip_index_set_coarse_device",
     "knhip_index_set_lists_device", "knhip_index_add_vectors_device", "knhip_index_count",
     "knhip_index_device_bytes", "knhip_index_uses_precomputed_table", "knhip_index_last_range_ranks", "knhip_search",
@@ -66,6 +66,10 @@ SYMBOLS = [
     "knhip_select_ordered_device",
     "knhip_iter_create", "knhip_iter_next", "knhip_iter_next_all", "knhip_iter_has_next", "knhip_iter_stats", "knhip_iter_destroy",
 ]
+
+
+# element type an IVF_FLAT index keeps its rows in on the device (knhip_index_set_row_type; the host boundary stays fp32)
+ROWTYPE_FP32, ROWTYPE_FP16, ROWTYPE_BF16 = 0, 1, 2
 
 
 def sq_code_size(dim, sq_type=8):
@@ -128,6 +132,9 @@ def load():
     L.knhip_index_set_sq_type.argtypes = [vp, i32]
     L.knhip_index_get_sq_type.argtypes = [vp]
     L.knhip_index_get_sq_type.restype = i32
+    L.knhip_index_set_row_type.argtypes = [vp, i32]
+    L.knhip_index_get_row_type.argtypes = [vp]
+    L.knhip_index_get_row_type.restype = i32
     L.knhip_index_set_row_scale.argtypes = [vp, vp, i32]
     L.knhip_index_add_assigned_by.argtypes = [vp, i64, vp, vp, vp]
     L.knhip_index_add_lists.argtypes = [vp, vp, vp, vp]

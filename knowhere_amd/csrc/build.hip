@@ -64,6 +64,8 @@ __global__ void idmap_cols_kernel(const int64_t* __restrict__ list_row_off, cons
 }
 
 // one thread per (requested id, chunk of 4 dims): binary search in the sorted ids, then the 16-byte piece of the row
+// (RT: rows kept as fp16 / bf16 -- a chunk is 8 dims, widened on the way out)
+template <int RT>
 __global__ void idmap_gather_kernel(const int64_t* __restrict__ want, int64_t n, const int64_t* __restrict__ ids_sorted,
                                     const int64_t* __restrict__ col_sorted, int64_t ntotal,
                                     const float4* __restrict__ rows, int d, int nchunk, float* __restrict__ out,
@@ -97,6 +99,15 @@ __global__ void idmap_gather_kernel(const int64_t* __restrict__ want, int64_t n,
         found[i] = 1;
     }
     const int64_t col = col_sorted[lo];
+    if constexpr (RT != KN_ROW_FP32) {
+        const uint4 w = reinterpret_cast<const uint4*>(rows)[(col >> 6) * (int64_t)nchunk * 64 + (int64_t)c * 64 + (col & 63)];
+        float y[8];
+        row_widen8<RT>(w, y);
+        for (int j = 0; j < 8 && c * 8 + j < d; j++) {
+            out[i * d + c * 8 + j] = y[j];
+        }
+        return;
+    }
     const float4 v = rows[(col >> 6) * (int64_t)nchunk * 64 + (int64_t)c * 64 + (col & 63)];
     const float e[4] = {v.x, v.y, v.z, v.w};
     for (int j = 0; j < 4 && c * 4 + j < d; j++) {
@@ -129,12 +140,19 @@ hipError_t launch_idmap_build(const int64_t* ids, const int64_t* list_row_off, c
 
 hipError_t launch_idmap_gather(const int64_t* want, int64_t n, const int64_t* ids_sorted, const int64_t* col_sorted,
                                int64_t ntotal, const float4* rows, int d, float* out, int32_t* missing, hipStream_t s,
-                               uint8_t* found) {
+                               uint8_t* found, int row_type) {
     if (n <= 0) {
         return hipSuccess;
     }
+    if (row_type != KN_ROW_FP32) {
+        const int nchunk8 = (d + 7) / 8;
+        auto kern = row_type == KN_ROW_BF16 ? idmap_gather_kernel<KN_ROW_BF16> : idmap_gather_kernel<KN_ROW_FP16>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((n * nchunk8 + 255) / 256)), dim3(256), 0, s, want, n, ids_sorted,
+                           col_sorted, ntotal, rows, d, nchunk8, out, missing, found);
+        return hipGetLastError();
+    }
     const int nchunk = (d + 3) / 4;
-    hipLaunchKernelGGL(idmap_gather_kernel, dim3((unsigned)((n * nchunk + 255) / 256)), dim3(256), 0, s, want, n,
+    hipLaunchKernelGGL(idmap_gather_kernel<KN_ROW_FP32>, dim3((unsigned)((n * nchunk + 255) / 256)), dim3(256), 0, s, want, n,
                        ids_sorted, col_sorted, ntotal, rows, d, nchunk, out, missing, found);
     return hipGetLastError();
 }

@@ -41,6 +41,40 @@ __device__ __forceinline__ float cosine_finish(float ip, float scale, int mode) 
     return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);
 }
 
+// ---- IVF-Flat rows kept narrow in HBM (knhip_index_set_row_type): RT = KN_ROW_FP16 / KN_ROW_BF16 --------------
+// One 16-byte chunk holds 8 dimensions.  Widening is exact (bf16: the pattern moved to the high half; fp16: one
+// conversion, subnormals and infinities included), so the fp32 arithmetic that follows gives the fp32 index's bits.
+template <int RT>
+__device__ __forceinline__ float row_widen(uint32_t h16) {
+    if (RT == knhip::KN_ROW_BF16) {
+        return __uint_as_float(h16 << 16);
+    }
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)h16);
+}
+template <int RT>
+__device__ __forceinline__ void row_widen8(const uint4& w, float (&y)[8]) {
+    const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        y[2 * e] = row_widen<RT>(ww[e] & 0xffffu);
+        y[2 * e + 1] = row_widen<RT>(ww[e] >> 16);
+    }
+}
+// acc over the 8 dimensions of a chunk against x[0..8), in dimension order: the steps of the fp32 kernels
+template <bool IS_L2, int RT>
+__device__ __forceinline__ float row_chunk8_steps(float acc, const uint4& w, const float* x) {
+    float y[8];
+    row_widen8<RT>(w, y);
+    const float4 x0 = *reinterpret_cast<const float4*>(x);
+    const float4 x1 = *reinterpret_cast<const float4*>(x + 4);
+    const float xx[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+        acc = IS_L2 ? l2_step(acc, xx[e], y[e]) : ip_step(acc, xx[e], y[e]);
+    }
+    return acc;
+}
+
 // ---- canonical ordering ----------------------------------------------------------------------
 // IS_L2: "a is better than b"  <=>  (da < db) || (da == db && ia < ib)
 // IP   :                         (da > db) || (da == db && ia > ib)

@@ -30,11 +30,13 @@ constexpr int FS_THREADS = FS_WAVES * KN_WAVE;
 
 // one work item (TABLE: `item_or_block` is the item when a.item_loop is set, else the block index that xcd_item
 // maps to an item; DENSE: the block index).  Every exit is workgroup-uniform.
-template <bool IS_L2, int QG, int R, bool DENSE>
+// RT: element type of the rows (kernels.h KN_ROW_*).  Typed rows are widened in registers and take the same steps in
+// the same order; the fp32 instantiation is the code it always was.
+template <bool IS_L2, int QG, int R, bool DENSE, int RT = KN_ROW_FP32>
 __device__ __forceinline__ void flat_scan_item(const FlatScanArgs& a, const int64_t item_or_block, unsigned char* smem) {
     const int lane = lane_id();
     const int wave = threadIdx.x / KN_WAVE;
-    const int dpad = a.nchunk * 4;
+    const int dpad = a.nchunk * (RT == KN_ROW_FP32 ? 4 : 8);
 
     // ---- decode the work item ----------------------------------------------------------
     int64_t item;
@@ -126,22 +128,34 @@ __device__ __forceinline__ void flat_scan_item(const FlatScanArgs& a, const int6
         // (one- and two-query items keep 8 row loads in flight: with so little arithmetic per load the scan is
         // latency-bound otherwise)
         constexpr int UF = QG <= 2 ? 8 : 2;
+        if constexpr (RT != KN_ROW_FP32) {
+            const uint4* p16 = reinterpret_cast<const uint4*>(p);
 #pragma unroll UF
-        for (int c = 0; c < a.nchunk; c++) {
-            const float4 y = p[(int64_t)c * 64];
+            for (int c = 0; c < a.nchunk; c++) {
+                const uint4 w = p16[(int64_t)c * 64];
 #pragma unroll
-            for (int j = 0; j < QG; j++) {
-                const float4 q = *reinterpret_cast<const float4*>(sq + j * dpad + c * 4);
-                if (IS_L2) {
-                    acc[j] = l2_step(acc[j], q.x, y.x);
-                    acc[j] = l2_step(acc[j], q.y, y.y);
-                    acc[j] = l2_step(acc[j], q.z, y.z);
-                    acc[j] = l2_step(acc[j], q.w, y.w);
-                } else {
-                    acc[j] = ip_step(acc[j], q.x, y.x);
-                    acc[j] = ip_step(acc[j], q.y, y.y);
-                    acc[j] = ip_step(acc[j], q.z, y.z);
-                    acc[j] = ip_step(acc[j], q.w, y.w);
+                for (int j = 0; j < QG; j++) {
+                    acc[j] = row_chunk8_steps<IS_L2, RT>(acc[j], w, sq + j * dpad + c * 8);
+                }
+            }
+        } else {
+#pragma unroll UF
+            for (int c = 0; c < a.nchunk; c++) {
+                const float4 y = p[(int64_t)c * 64];
+#pragma unroll
+                for (int j = 0; j < QG; j++) {
+                    const float4 q = *reinterpret_cast<const float4*>(sq + j * dpad + c * 4);
+                    if (IS_L2) {
+                        acc[j] = l2_step(acc[j], q.x, y.x);
+                        acc[j] = l2_step(acc[j], q.y, y.y);
+                        acc[j] = l2_step(acc[j], q.z, y.z);
+                        acc[j] = l2_step(acc[j], q.w, y.w);
+                    } else {
+                        acc[j] = ip_step(acc[j], q.x, y.x);
+                        acc[j] = ip_step(acc[j], q.y, y.y);
+                        acc[j] = ip_step(acc[j], q.z, y.z);
+                        acc[j] = ip_step(acc[j], q.w, y.w);
+                    }
                 }
             }
         }
@@ -241,24 +255,24 @@ __device__ __forceinline__ void flat_scan_item(const FlatScanArgs& a, const int6
     }
 }
 
-template <bool IS_L2, int QG, int R, bool DENSE>
+template <bool IS_L2, int QG, int R, bool DENSE, int RT = KN_ROW_FP32>
 __global__ __launch_bounds__(FS_THREADS) void flat_scan_kernel(FlatScanArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     if (!DENSE && a.item_loop) {
         // a fixed grid walks an item table whose size only the device knows (mfma_scan.hip fallback)
         const int64_t nitems = *a.nitems_dev;
         for (int64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
-            flat_scan_item<IS_L2, QG, R, DENSE>(a, item, smem);
+            flat_scan_item<IS_L2, QG, R, DENSE, RT>(a, item, smem);
             __syncthreads();
         }
         return;
     }
-    flat_scan_item<IS_L2, QG, R, DENSE>(a, blockIdx.x, smem);
+    flat_scan_item<IS_L2, QG, R, DENSE, RT>(a, blockIdx.x, smem);
 }
 
 // ---- all-pairs exact distances (coarse quantizer, exact mode / fallback) ----------------------
 // out[q][row] for every query and every row of a DENSE row set.  Same arithmetic as above.
-template <bool IS_L2, int QG>
+template <bool IS_L2, int QG, int RT = KN_ROW_FP32>
 __global__ __launch_bounds__(FS_THREADS) void flat_full_kernel(FlatScanArgs a, float* out,
                                                                const int32_t* q_subset,
                                                                int64_t nq_subset,
@@ -266,7 +280,7 @@ __global__ __launch_bounds__(FS_THREADS) void flat_full_kernel(FlatScanArgs a, f
     extern __shared__ __align__(16) unsigned char smem[];
     const int lane = lane_id();
     const int wave = threadIdx.x / KN_WAVE;
-    const int dpad = a.nchunk * 4;
+    const int dpad = a.nchunk * (RT == KN_ROW_FP32 ? 4 : 8);
     const int64_t nq = q_subset ? nq_subset : a.nq;
     const int64_t ngroups = (nq + QG - 1) / QG;
     // With row flags (the exact fallback of the MFMA prefilter) the grid is small and walks the items: row_flags[a.nq] is
@@ -315,22 +329,34 @@ __global__ __launch_bounds__(FS_THREADS) void flat_full_kernel(FlatScanArgs a, f
         for (int j = 0; j < QG; j++) {
             acc[j] = 0.f;
         }
+        if constexpr (RT != KN_ROW_FP32) {
+            const uint4* p16 = reinterpret_cast<const uint4*>(p);
 #pragma unroll 2
-        for (int c = 0; c < a.nchunk; c++) {
-            const float4 y = p[(int64_t)c * 64];
+            for (int c = 0; c < a.nchunk; c++) {
+                const uint4 w = p16[(int64_t)c * 64];
 #pragma unroll
-            for (int j = 0; j < QG; j++) {
-                const float4 q = *reinterpret_cast<const float4*>(sq + j * dpad + c * 4);
-                if (IS_L2) {
-                    acc[j] = l2_step(acc[j], q.x, y.x);
-                    acc[j] = l2_step(acc[j], q.y, y.y);
-                    acc[j] = l2_step(acc[j], q.z, y.z);
-                    acc[j] = l2_step(acc[j], q.w, y.w);
-                } else {
-                    acc[j] = ip_step(acc[j], q.x, y.x);
-                    acc[j] = ip_step(acc[j], q.y, y.y);
-                    acc[j] = ip_step(acc[j], q.z, y.z);
-                    acc[j] = ip_step(acc[j], q.w, y.w);
+                for (int j = 0; j < QG; j++) {
+                    acc[j] = row_chunk8_steps<IS_L2, RT>(acc[j], w, sq + j * dpad + c * 8);
+                }
+            }
+        } else {
+#pragma unroll 2
+            for (int c = 0; c < a.nchunk; c++) {
+                const float4 y = p[(int64_t)c * 64];
+#pragma unroll
+                for (int j = 0; j < QG; j++) {
+                    const float4 q = *reinterpret_cast<const float4*>(sq + j * dpad + c * 4);
+                    if (IS_L2) {
+                        acc[j] = l2_step(acc[j], q.x, y.x);
+                        acc[j] = l2_step(acc[j], q.y, y.y);
+                        acc[j] = l2_step(acc[j], q.z, y.z);
+                        acc[j] = l2_step(acc[j], q.w, y.w);
+                    } else {
+                        acc[j] = ip_step(acc[j], q.x, y.x);
+                        acc[j] = ip_step(acc[j], q.y, y.y);
+                        acc[j] = ip_step(acc[j], q.z, y.z);
+                        acc[j] = ip_step(acc[j], q.w, y.w);
+                    }
                 }
             }
         }
@@ -416,6 +442,96 @@ __global__ void interleave_lists_kernel(const float* __restrict__ src,
 // ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
+// ---- typed IVF-Flat rows: narrow + check, widen, interleave ------------------------------------------------------------
+// (here, beside the fp32 interleave kernels, and not in build.hip: the emulated library of tests/hipemu leaves build.hip out)
+// One thread per value; the rule is row_narrow (kernels.h).
+__global__ void rows_narrow_check_kernel(const uint32_t* __restrict__ x, int64_t nval, int row_type,
+                                         uint16_t* __restrict__ out, unsigned long long* __restrict__ first_bad) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nval) {
+        return;
+    }
+    uint32_t h = 0;
+    if (!row_narrow(x[t], row_type, &h)) {
+        atomicMin(first_bad, (unsigned long long)t);
+    }
+    out[t] = (uint16_t)h;
+}
+
+template <int RT>
+__global__ void rows_widen_kernel(const uint16_t* __restrict__ x, int64_t nval, float* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < nval) {
+        out[t] = row_widen<RT>(x[t]);
+    }
+}
+
+// list-sorted narrow rows [ntotal][d] -> per-list interleaved blocks of 16-byte chunks (8 dimensions, zero padded)
+__global__ void interleave_lists16_kernel(const uint16_t* __restrict__ src, const int64_t* __restrict__ list_row_off,
+                                          const int64_t* __restrict__ list_len,
+                                          const int64_t* __restrict__ list_blk_off, int64_t nlist, int d, int nchunk,
+                                          uint4* __restrict__ dst) {
+    const int64_t l = blockIdx.y + (int64_t)blockIdx.z * gridDim.y;
+    if (l >= nlist) {
+        return;
+    }
+    const int64_t len = list_len[l];
+    const int64_t nblk = (len + 63) / 64;
+    const int64_t row_off = list_row_off[l];
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nblk * nchunk * 64;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = t / ((int64_t)nchunk * 64);
+        const int rem = (int)(t % ((int64_t)nchunk * 64));
+        const int c = rem / 64, r = rem % 64;
+        const int64_t row = b * 64 + r;
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        if (row < len) {
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                const int i = c * 8 + e;
+                if (i < d) {
+                    w[e >> 1] |= (uint32_t)src[(row_off + row) * d + i] << (16 * (e & 1));
+                }
+            }
+        }
+        dst[(list_blk_off[l] + b) * (int64_t)nchunk * 64 + rem] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+hipError_t launch_rows_narrow_check(const float* x, int64_t n, int d, int row_type, uint16_t* out,
+                                    unsigned long long* first_bad, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(first_bad, 0xff, sizeof(unsigned long long), s);
+    const int64_t nval = n * d;
+    if (e != hipSuccess || nval <= 0) {
+        return e;
+    }
+    hipLaunchKernelGGL(rows_narrow_check_kernel, dim3((unsigned)((nval + 255) / 256)), dim3(256), 0, s,
+                       reinterpret_cast<const uint32_t*>(x), nval, row_type, out, first_bad);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_widen(const uint16_t* x, int64_t n_values, int row_type, float* out, hipStream_t s) {
+    if (n_values <= 0) {
+        return hipSuccess;
+    }
+    auto kern = row_type == KN_ROW_BF16 ? rows_widen_kernel<KN_ROW_BF16> : rows_widen_kernel<KN_ROW_FP16>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((n_values + 255) / 256)), dim3(256), 0, s, x, n_values, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_interleave_lists16(const uint16_t* src, const int64_t* list_row_off, const int64_t* list_len,
+                                     const int64_t* list_blk_off, int64_t nlist, int d, uint4* dst, hipStream_t s) {
+    if (nlist <= 0) {
+        return hipSuccess;
+    }
+    const int nchunk = (d + 7) / 8;
+    const unsigned gy = (unsigned)std::min<int64_t>(nlist, 32768);
+    const unsigned gz = (unsigned)((nlist + gy - 1) / gy);
+    hipLaunchKernelGGL(interleave_lists16_kernel, dim3(8, gy, gz), dim3(256), 0, s, src, list_row_off, list_len,
+                       list_blk_off, nlist, d, nchunk, dst);
+    return hipGetLastError();
+}
+
 static size_t flat_scan_smem(int QG, int dpad, int k) {
     const size_t qbytes = (size_t)QG * dpad * 4;
     const int qr = std::max(1, std::min(QG, (int)(48 * 1024 / (FS_WAVES * k * 12))));
@@ -427,14 +543,14 @@ int flat_scan_qg(int k) {
     return k <= 128 ? 8 : (k <= 256 ? 4 : (k <= 512 ? 2 : 1));
 }
 
-template <bool IS_L2, bool DENSE>
+template <bool IS_L2, bool DENSE, int RT = KN_ROW_FP32>
 static hipError_t launch_flat_scan_t(const FlatScanArgs& a, int64_t grid, hipStream_t s, int qg_override) {
-    const int dpad = a.nchunk * 4;
+    const int dpad = a.nchunk * (RT == KN_ROW_FP32 ? 4 : 8);
     const int k = a.k;
 #define FS_LAUNCH(QG_, R_)                                                                         \
     do {                                                                                           \
         const size_t sm = flat_scan_smem(QG_, dpad, k);                                            \
-        auto kern = flat_scan_kernel<IS_L2, QG_, R_, DENSE>;                                       \
+        auto kern = flat_scan_kernel<IS_L2, QG_, R_, DENSE, RT>;                                       \
         if (sm > 48 * 1024) {                                                                      \
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
@@ -477,6 +593,17 @@ hipError_t launch_flat_scan(const FlatScanArgs& a, bool is_l2, bool dense, int64
     if (!a.item_loop) {
         grid = (grid + 7) / 8 * 8; // (xcd_item spreads the items over the blocks [0, round_up(nitems, 8)))
     }
+    if (a.row_type != KN_ROW_FP32) { // (typed rows: the lists of an IVF-Flat index)
+        if (dense || (a.row_type != KN_ROW_FP16 && a.row_type != KN_ROW_BF16)) {
+            return hipErrorInvalidValue;
+        }
+        if (a.row_type == KN_ROW_FP16) {
+            return is_l2 ? launch_flat_scan_t<true, false, KN_ROW_FP16>(a, grid, s, qg_override)
+                         : launch_flat_scan_t<false, false, KN_ROW_FP16>(a, grid, s, qg_override);
+        }
+        return is_l2 ? launch_flat_scan_t<true, false, KN_ROW_BF16>(a, grid, s, qg_override)
+                     : launch_flat_scan_t<false, false, KN_ROW_BF16>(a, grid, s, qg_override);
+    }
     if (is_l2) {
         return dense ? launch_flat_scan_t<true, true>(a, grid, s, 0)
                      : launch_flat_scan_t<true, false>(a, grid, s, qg_override);
@@ -494,8 +621,15 @@ hipError_t launch_flat_full(const FlatScanArgs& a, bool is_l2, float* out, const
     }
     const int64_t ngroups = (nq + QG - 1) / QG;
     const int64_t nchunks = (a.nrows + a.chunk_rows - 1) / a.chunk_rows;
-    const size_t sm = (size_t)QG * a.nchunk * 4 * 4;
+    const size_t sm = (size_t)QG * a.nchunk * row_chunk_dims(a.row_type) * 4;
     auto kern = is_l2 ? flat_full_kernel<true, QG> : flat_full_kernel<false, QG>;
+    if (a.row_type == KN_ROW_FP16) { // (every list of a typed IVF-Flat index as one row set: range search over all lists)
+        kern = is_l2 ? flat_full_kernel<true, QG, KN_ROW_FP16> : flat_full_kernel<false, QG, KN_ROW_FP16>;
+    } else if (a.row_type == KN_ROW_BF16) {
+        kern = is_l2 ? flat_full_kernel<true, QG, KN_ROW_BF16> : flat_full_kernel<false, QG, KN_ROW_BF16>;
+    } else if (a.row_type != KN_ROW_FP32) {
+        return hipErrorInvalidValue;
+    }
     if (sm > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);

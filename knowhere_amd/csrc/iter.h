@@ -59,6 +59,7 @@ struct IterScanArgs {
     const float* centroids;
     const float* trained; // IVF-SQ: vmin[d], vdiff[d]
     int32_t sq_bits;      // IVF-SQ: code width 8, 6 or 4 (0 = 8)
+    int32_t row_type;     // IVF-Flat: KN_ROW_* of the rows
     const float* row_scale;
     int32_t cos_mode;
     int32_t id_desc;

@@ -72,7 +72,8 @@ __global__ __launch_bounds__(IT_THREADS) void iter_accept_kernel(IterScanArgs a,
 }
 
 // ---- exact distances of the round's lists -> the segments ---------------------------------------------------------------
-template <bool IS_L2, int KIND, int BITS = 8>
+// (RT: IVF-Flat rows kept as fp16 / bf16 are widened in registers and take the fp32 steps)
+template <bool IS_L2, int KIND, int BITS = 8, int RT = KN_ROW_FP32>
 __global__ __launch_bounds__(IT_THREADS) void iter_expand_kernel(IterScanArgs a, const IterWork* __restrict__ works,
                                                                  const IterPair* __restrict__ pairs, int64_t nchunk_max) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -89,8 +90,8 @@ __global__ __launch_bounds__(IT_THREADS) void iter_expand_kernel(IterScanArgs a,
     const int64_t row = b * 64 + lane;
     float acc = 0.f;
     if (KIND == KNHIP_IVF_FLAT) {
-        const int nchunk = (a.d + 3) / 4;
-        const int dpad = nchunk * 4;
+        const int nchunk = RT == KN_ROW_FP32 ? (a.d + 3) / 4 : (a.d + 7) / 8;
+        const int dpad = nchunk * (RT == KN_ROW_FP32 ? 4 : 8);
         float* sq = reinterpret_cast<float*>(smem);
         for (int i = threadIdx.x; i < dpad; i += IT_THREADS) {
             sq[i] = (i < a.d) ? a.queries[wk.q * a.d + i] : 0.f;
@@ -98,20 +99,28 @@ __global__ __launch_bounds__(IT_THREADS) void iter_expand_kernel(IterScanArgs a,
         __syncthreads();
         if (b * 64 < len) {
             const float4* p = reinterpret_cast<const float4*>(a.rows) + (blk0 + b) * (int64_t)nchunk * 64 + lane;
+            if constexpr (RT != KN_ROW_FP32) {
+                const uint4* p16 = reinterpret_cast<const uint4*>(p);
 #pragma unroll 4
-            for (int c = 0; c < nchunk; c++) {
-                const float4 y = p[(int64_t)c * 64];
-                const float4 x = *reinterpret_cast<const float4*>(sq + c * 4);
-                if (IS_L2) {
-                    acc = l2_step(acc, x.x, y.x);
-                    acc = l2_step(acc, x.y, y.y);
-                    acc = l2_step(acc, x.z, y.z);
-                    acc = l2_step(acc, x.w, y.w);
-                } else {
-                    acc = ip_step(acc, x.x, y.x);
-                    acc = ip_step(acc, x.y, y.y);
-                    acc = ip_step(acc, x.z, y.z);
-                    acc = ip_step(acc, x.w, y.w);
+                for (int c = 0; c < nchunk; c++) {
+                    acc = row_chunk8_steps<IS_L2, RT>(acc, p16[(int64_t)c * 64], sq + c * 8);
+                }
+            } else {
+#pragma unroll 4
+                for (int c = 0; c < nchunk; c++) {
+                    const float4 y = p[(int64_t)c * 64];
+                    const float4 x = *reinterpret_cast<const float4*>(sq + c * 4);
+                    if (IS_L2) {
+                        acc = l2_step(acc, x.x, y.x);
+                        acc = l2_step(acc, x.y, y.y);
+                        acc = l2_step(acc, x.z, y.z);
+                        acc = l2_step(acc, x.w, y.w);
+                    } else {
+                        acc = ip_step(acc, x.x, y.x);
+                        acc = ip_step(acc, x.y, y.y);
+                        acc = ip_step(acc, x.z, y.z);
+                        acc = ip_step(acc, x.w, y.w);
+                    }
                 }
             }
             if (!IS_L2 && a.cos_mode != 0 && row < len) {
@@ -463,8 +472,15 @@ hipError_t launch_iter_expand(const IterScanArgs& a, bool is_l2, const IterWork*
     }
     const dim3 grid((unsigned)(npairs * nchunk));
     if (a.kind == KNHIP_IVF_FLAT) {
-        const size_t lds = (size_t)((a.d + 3) / 4) * 4 * sizeof(float);
+        const size_t lds = (size_t)row_nchunk(a.d, a.row_type) * row_chunk_dims(a.row_type) * sizeof(float);
         auto kern = is_l2 ? iter_expand_kernel<true, KNHIP_IVF_FLAT> : iter_expand_kernel<false, KNHIP_IVF_FLAT>;
+        if (a.row_type == KN_ROW_FP16) {
+            kern = is_l2 ? iter_expand_kernel<true, KNHIP_IVF_FLAT, 8, KN_ROW_FP16> : iter_expand_kernel<false, KNHIP_IVF_FLAT, 8, KN_ROW_FP16>;
+        } else if (a.row_type == KN_ROW_BF16) {
+            kern = is_l2 ? iter_expand_kernel<true, KNHIP_IVF_FLAT, 8, KN_ROW_BF16> : iter_expand_kernel<false, KNHIP_IVF_FLAT, 8, KN_ROW_BF16>;
+        } else if (a.row_type != KN_ROW_FP32) {
+            return hipErrorInvalidValue;
+        }
         hipLaunchKernelGGL(kern, grid, dim3(IT_THREADS), lds, s, a, works, pairs, nchunk);
     } else if (a.kind == KNHIP_IVF_SQ8) {
         const int bits = a.sq_bits == 0 ? 8 : a.sq_bits;

@@ -86,9 +86,51 @@ struct P16Rec {
 };
 static_assert(sizeof(P16Rec) == 256, "P16Rec layout");
 
+// element type of the resident IVF-Flat rows (= KNHIP_ROWTYPE_* of include/knhip.h)
+enum { KN_ROW_FP32 = 0, KN_ROW_FP16 = 1, KN_ROW_BF16 = 2 };
+// 16-byte chunks of a row in the interleaved blocks: 4 fp32 dimensions, or 8 narrow ones (zero padded)
+inline int row_chunk_dims(int row_type) { return row_type == KN_ROW_FP32 ? 4 : 8; }
+inline int row_nchunk(int d, int row_type) { return row_type == KN_ROW_FP32 ? (d + 3) / 4 : (d + 7) / 8; }
+
+// The representability rule of typed IVF-Flat rows (device: rows_narrow_check_kernel; host: the up-front check of a
+// sliced knhip_index_add).  A value passes only if widening the narrow pattern gives back its 32 bits -- integer logic
+// throughout, so subnormals never meet a flush-to-zero mode.  bf16: low half zero, no NaN.  fp16: +-0, +-inf, the
+// normals 2^-14 .. 65504 (biased fp32 exponent 113 .. 142, 13 low mantissa bits zero) and the subnormals k 2^-24 (exponent
+// 103 .. 112, the value a multiple of 2^-24: 126 - e low mantissa bits zero).
+__host__ __device__ inline bool row_narrow(uint32_t u, int row_type, uint32_t* out) {
+    const uint32_t a = u & 0x7fffffffu;
+    if (a > 0x7f800000u) {
+        return false; // NaN
+    }
+    if (row_type == KN_ROW_BF16) {
+        *out = u >> 16;
+        return (u & 0xffffu) == 0u;
+    }
+    const uint32_t sign = (u >> 16) & 0x8000u;
+    const uint32_t e = a >> 23, m = a & 0x7fffffu;
+    if (a == 0u) {
+        *out = sign;
+        return true;
+    }
+    if (a == 0x7f800000u) {
+        *out = sign | 0x7c00u;
+        return true;
+    }
+    if (e >= 113u && e <= 142u) {
+        *out = sign | ((e - 112u) << 10) | (m >> 13);
+        return (m & 0x1fffu) == 0u;
+    }
+    if (e >= 103u && e <= 112u) {
+        const uint32_t sh = 126u - e; // 14 .. 23
+        *out = sign | ((0x800000u | m) >> sh);
+        return (m & ((1u << sh) - 1u)) == 0u;
+    }
+    return false;
+}
+
 struct FlatScanArgs {
     // rows
-    const float4* rows;          // interleaved blocks
+    const float4* rows;          // interleaved blocks (row_type != 0: 16-byte chunks of 8 narrow values, read as uint4)
     const int64_t* list_blk_off; // [nlist] first block of each list (TABLE) / nullptr (DENSE)
     const int64_t* list_len;     // [nlist] rows in each list (TABLE)
     const int64_t* list_row_off; // [nlist] first entry in ids[] of each list (TABLE)
@@ -97,7 +139,8 @@ struct FlatScanArgs {
     int64_t chunk_rows;          // DENSE: rows per chunk (multiple of 64)
     int64_t id_offset;           // DENSE
     int32_t d;
-    int32_t nchunk;              // ceil(d/4)
+    int32_t nchunk;              // ceil(d/4); typed rows: ceil(d/8)
+    int32_t row_type;            // KN_ROW_* (the lists of an IVF-Flat index; every other row set is fp32)
     // queries
     const float* queries;        // [nq][d]
     int64_t nq;
@@ -217,6 +260,8 @@ struct MScanArgs {
     int32_t nstep;               // fp32: ceil(nchunk / 4) steps of 16 dims; IVF-SQ: steps of 32 dims (8 bits: two chunks) or
                                  // 64 dims (4 bits: two chunks, 6 bits: three) -- sq_codec.h SqStep
     int32_t sq_bits;             // IVF-SQ: code width 8, 6 or 4 (0 = 8)
+    int32_t row_type;            // IVF-Flat: KN_ROW_* of the rows; typed rows: nchunk = ceil(d / 8) chunks of 8 dims, nstep = steps
+                                 // of 16 dims (two chunks)
     const float* queries;
     const float* qnorm;          // [nq] ||q||^2 (fp32 rows)
     const float* coarse_dis;     // [nq][nslot] (SQ8 IP: accu0)
@@ -337,6 +382,14 @@ hipError_t launch_flat_full(const FlatScanArgs& a, bool is_l2, float* out, const
                             int64_t nq_subset, const int32_t* row_flags, hipStream_t s);
 hipError_t launch_interleave_rows(const float* src, int64_t n, int d, float4* dst, int64_t dst_blk0,
                                   hipStream_t s);
+// typed IVF-Flat rows (flat_scan.hip).  narrow: x [n][d] fp32 -> out [n][d] 16-bit patterns; *first_bad (initialised to
+// ~0 by the launcher) = the smallest row * d + dim whose value the type cannot hold (then `out` is not to be used).  widen:
+// the inverse, exact.  interleave: list-sorted narrow rows -> 64-row blocks of 16-byte chunks of 8 dimensions
+hipError_t launch_rows_narrow_check(const float* x, int64_t n, int d, int row_type, uint16_t* out,
+                                    unsigned long long* first_bad, hipStream_t s);
+hipError_t launch_rows_widen(const uint16_t* x, int64_t n_values, int row_type, float* out, hipStream_t s);
+hipError_t launch_interleave_lists16(const uint16_t* src, const int64_t* list_row_off, const int64_t* list_len,
+                                     const int64_t* list_blk_off, int64_t nlist, int d, uint4* dst, hipStream_t s);
 hipError_t launch_interleave_lists(const float* src, const int64_t* list_row_off,
                                    const int64_t* list_len, const int64_t* list_blk_off, int64_t nlist,
                                    int d, float4* dst, hipStream_t s);
@@ -378,7 +431,7 @@ size_t mscan_sq8_smem(int nstep, int bits = 8);
 int mscan_finish_pmax(int cap, int k);
 int mscan_sample_rows();
 hipError_t launch_ms_block_norms(const float4* rows, int64_t total_blk, int nchunk, float* out, float* out_max,
-                                 hipStream_t s);
+                                 hipStream_t s, int row_type = KN_ROW_FP32);
 hipError_t launch_ms_sq8_norms(const uint4* rows, int64_t total_blk, int nchunk16, int d, const float* trained,
                                float* out, float* out_max, hipStream_t s, int bits = 8);
 // units from one virtual-list range of the work table (`*_v` = the table's arrays offset to that range).
@@ -661,7 +714,8 @@ hipError_t launch_idmap_build(const int64_t* ids, const int64_t* list_row_off, c
                               size_t tmp_bytes, hipStream_t s);
 hipError_t launch_idmap_gather(const int64_t* want, int64_t n, const int64_t* ids_sorted, const int64_t* col_sorted,
                                int64_t ntotal, const float4* rows, int d, float* out, int32_t* missing, hipStream_t s,
-                               uint8_t* found = nullptr); // found [n] (optional): 1 = the id is stored here, its row was written
+                               uint8_t* found = nullptr, // found [n] (optional): 1 = the id is stored here, its row was written
+                               int row_type = KN_ROW_FP32); // (rows of a typed IVF-Flat index: widened to fp32)
 hipError_t launch_gather_rows(const float* x, const int64_t* rows, int64_t n, int d, float* out, hipStream_t s);
 hipError_t launch_residual(const float* x, const float* cen, const int64_t* assign, int64_t n, int d, float* out,
                            hipStream_t s);

@@ -195,6 +195,25 @@ int build_pq_skew(const knhip_index* cidx) {
 // set it to 0 to exercise the rebuild path)
 size_t aos_keep_limit() { return env_layout().aos_keep_bytes; }
 
+int narrow_rows(const knhip_index* idx, int64_t n, const float* d_x, DevBuf& out, const char* who) {
+    static_assert(KNHIP_ROWTYPE_FP32 == KN_ROW_FP32 && KNHIP_ROWTYPE_FP16 == KN_ROW_FP16 && KNHIP_ROWTYPE_BF16 == KN_ROW_BF16,
+                  "the kernels' row types are the ABI's");
+    DevBuf bad;
+    HIP_TRY(out.alloc((size_t)std::max<int64_t>(n, 1) * idx->d * sizeof(uint16_t)));
+    HIP_TRY(bad.alloc(sizeof(unsigned long long)));
+    HIP_TRY(launch_rows_narrow_check(d_x, n, idx->d, idx->row_type, out.as<uint16_t>(), bad.as<unsigned long long>(), nullptr));
+    unsigned long long first = 0;
+    HIP_TRY(hipMemcpy(&first, bad.p, sizeof(first), hipMemcpyDeviceToHost));
+    if (first != ~0ull) {
+        const char* tname = idx->row_type == KNHIP_ROWTYPE_BF16 ? "bf16" : "fp16";
+        return fail(KNHIP_ERR_INVALID_ARGS, std::string(who) + ": row_type " + tname + " cannot hold the value at row " +
+                                                    std::to_string(first / (unsigned long long)idx->d) + ", dimension " +
+                                                    std::to_string(first % (unsigned long long)idx->d) +
+                                                    " exactly (nothing is rounded; the index is unchanged)");
+    }
+    return KNHIP_OK;
+}
+
 // lay the lists out from device-resident, list-sorted AoS codes + ids
 int build_list_layout(knhip_index* idx, const std::vector<int64_t>& list_off, const uint8_t* d_codes,
                       const int64_t* d_ids) {
@@ -264,7 +283,7 @@ int build_list_layout(knhip_index* idx, const std::vector<int64_t>& list_off, co
     }
     // the canonical AoS bytes stay resident for IVF_PQ (they feed the lazily built layouts; 32 B / row) and for small
     // flat / SQ8 indexes; large flat / SQ8 lists keep only the interleaved layout (C5: 76.8 GB of codes once, not twice)
-    const size_t aos_bytes = (size_t)ntotal * idx->code_size;
+    const size_t aos_bytes = (size_t)ntotal * idx->dev_code_size();
     const bool keep_aos = kind == KNHIP_IVF_PQ || aos_bytes <= aos_keep_limit();
     if (idx->codes_aos.p != d_codes) {
         idx->codes_aos.release();
@@ -279,7 +298,14 @@ int build_list_layout(knhip_index* idx, const std::vector<int64_t>& list_off, co
     const int64_t total_blk = blk_off[nlist];
     idx->total_blk = total_blk;
     idx->h_list_blk_off = blk_off;
-    if (kind == KNHIP_IVF_FLAT) {
+    if (kind == KNHIP_IVF_FLAT && idx->row_type != KNHIP_ROWTYPE_FP32) {
+        // rows kept as fp16 / bf16 (d_codes: the narrowed rows): 64-row blocks of 16-byte chunks of 8 dimensions
+        const int nchunk = row_nchunk(idx->d, idx->row_type);
+        HIP_TRY(idx->rows.alloc((size_t)total_blk * nchunk * 64 * sizeof(uint4)));
+        HIP_TRY(launch_interleave_lists16(reinterpret_cast<const uint16_t*>(d_codes), idx->d_list_row_off.as<int64_t>(),
+                                          idx->d_list_len.as<int64_t>(), idx->d_list_blk_off.as<int64_t>(), nlist, idx->d,
+                                          idx->rows.as<uint4>(), nullptr));
+    } else if (kind == KNHIP_IVF_FLAT) {
         const int nchunk = (idx->d + 3) / 4;
         HIP_TRY(idx->rows.alloc((size_t)total_blk * nchunk * 64 * sizeof(float4)));
         HIP_TRY(launch_interleave_lists(reinterpret_cast<const float*>(d_codes),
@@ -329,10 +355,11 @@ int ensure_aos(const knhip_index* cidx) {
     if (idx->aos_ready || !idx->has_data || idx->desc.kind == KNHIP_BRUTE_FORCE) {
         return KNHIP_OK;
     }
-    HIP_TRY(idx->codes_aos.alloc((size_t)std::max<int64_t>(idx->ntotal, 1) * idx->code_size));
+    // (typed IVF-Flat rows: 2 d bytes per row, in chunks of 16 -- the same byte mover)
+    HIP_TRY(idx->codes_aos.alloc((size_t)std::max<int64_t>(idx->ntotal, 1) * idx->dev_code_size()));
     HIP_TRY(launch_deinterleave_lists(idx->rows.as<uint4>(), idx->d_list_row_off.as<int64_t>(),
                                       idx->d_list_len.as<int64_t>(), idx->d_list_blk_off.as<int64_t>(), idx->nlist,
-                                      idx->code_size, idx->codes_aos.as<uint8_t>(), nullptr));
+                                      idx->dev_code_size(), idx->codes_aos.as<uint8_t>(), nullptr));
     HIP_TRY(hipDeviceSynchronize());
     idx->aos_ready = true;
     return KNHIP_OK;
@@ -349,7 +376,8 @@ int ensure_mscan_norms(const knhip_index* idx) {
     float* xn = idx->xnorm.as<float>();
     float* xmax = xn + std::max<int64_t>(total_blk, 1) * 64;
     if (idx->desc.kind == KNHIP_IVF_FLAT) {
-        HIP_TRY(launch_ms_block_norms(idx->rows.as<float4>(), total_blk, (idx->d + 3) / 4, xn, xmax, nullptr));
+        HIP_TRY(launch_ms_block_norms(idx->rows.as<float4>(), total_blk, row_nchunk(idx->d, idx->row_type), xn, xmax, nullptr,
+                                      idx->row_type));
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(&idx->xnorm_max, xmax, sizeof(float), hipMemcpyDeviceToHost));
     } else {
@@ -734,6 +762,28 @@ int32_t knhip_index_get_sq_type(const knhip_index* idx) {
     return idx->sq_bits;
 }
 
+int knhip_index_set_row_type(knhip_index* idx, int32_t row_type) {
+    if (int rc = check_index(idx)) return rc;
+    if (row_type == KNHIP_ROWTYPE_FP32) {
+        return KNHIP_OK; // (what every index holds unless told otherwise)
+    }
+    if (idx->desc.kind != KNHIP_IVF_FLAT || (row_type != KNHIP_ROWTYPE_FP16 && row_type != KNHIP_ROWTYPE_BF16)) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "set_row_type: an IVF_FLAT index and a row type of fp32 (0), fp16 (1) or bf16 (2)");
+    }
+    if (idx->has_data) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "set_row_type: the index already holds rows");
+    }
+    idx->row_type = row_type;
+    return KNHIP_OK;
+}
+
+int32_t knhip_index_get_row_type(const knhip_index* idx) {
+    if (!idx || idx->desc.kind != KNHIP_IVF_FLAT) {
+        return 0;
+    }
+    return idx->row_type;
+}
+
 int knhip_index_set_row_scale(knhip_index* idx, const float* scale, int32_t mode) {
     if (int rc = check_index(idx)) return rc;
     const int kind = idx->desc.kind;
@@ -838,9 +888,13 @@ int knhip_index_add_lists(knhip_index* idx, const int64_t* list_sizes, const uin
             }
         }
     }
-    DevBuf dc, di;
+    DevBuf dc, di, dn;
     if (int rc = upload(dc, hc.data(), hc.size())) return rc;
     if (int rc = upload(di, hi.data(), hi.size() * sizeof(int64_t))) return rc;
+    if (idx->row_type != KNHIP_ROWTYPE_FP32) { // (rows in list order: the row named in a refusal counts from list 0)
+        if (int rc = narrow_rows(idx, ntotal, dc.as<float>(), dn, "add_lists")) return rc;
+        return build_list_layout(idx, off, dn.as<uint8_t>(), di.as<int64_t>());
+    }
     return build_list_layout(idx, off, dc.as<uint8_t>(), di.as<int64_t>());
 }
 
@@ -854,6 +908,11 @@ int knhip_index_set_lists_device(knhip_index* idx, const int64_t* list_offsets, 
     std::vector<int64_t> off(list_offsets, list_offsets + idx->nlist + 1);
     if (off[0] != 0) {
         return fail(KNHIP_ERR_INVALID_ARGS, "list_offsets[0] must be 0");
+    }
+    if (idx->row_type != KNHIP_ROWTYPE_FP32) {
+        DevBuf dn;
+        if (int rc = narrow_rows(idx, off[idx->nlist], reinterpret_cast<const float*>(d_codes), dn, "set_lists_device")) return rc;
+        return build_list_layout(idx, off, dn.as<uint8_t>(), d_ids);
     }
     return build_list_layout(idx, off, d_codes, d_ids);
 }
@@ -1226,7 +1285,7 @@ int knhip_index_get_vectors(const knhip_index* idx, int64_t n, const int64_t* id
         HIP_TRY(hipMemset(dmiss.p, 0, sizeof(int32_t)));
         HIP_TRY(launch_idmap_gather(dw.as<int64_t>(), n, idx->idmap_ids.as<int64_t>(), idx->idmap_col.as<int64_t>(),
                                     idx->ntotal, idx->rows.as<float4>(), idx->d, dout.as<float>(), dmiss.as<int32_t>(),
-                                    nullptr));
+                                    nullptr, nullptr, idx->row_type));
         int32_t miss = 0;
         HIP_TRY(hipMemcpy(&miss, dmiss.p, sizeof(int32_t), hipMemcpyDeviceToHost));
         if (miss != 0) {
@@ -1301,7 +1360,7 @@ int knhip_index_find_vectors(const knhip_index* idx, int64_t n, const int64_t* i
     HIP_TRY(hipMemset(dfound.p, 0, (size_t)n));
     HIP_TRY(launch_idmap_gather(dw.as<int64_t>(), n, idx->idmap_ids.as<int64_t>(), idx->idmap_col.as<int64_t>(), idx->ntotal,
                                 idx->rows.as<float4>(), d, dout.as<float>(), dmiss.as<int32_t>(), nullptr,
-                                dfound.as<uint8_t>()));
+                                dfound.as<uint8_t>(), idx->row_type));
     std::vector<float> tmp((size_t)n * d);
     HIP_TRY(hipMemcpy(found, dfound.p, (size_t)n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(tmp.data(), dout.p, tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -1654,6 +1713,11 @@ int knhip_index_get_lists(const knhip_index* idx, uint8_t* codes, int64_t* ids) 
                     }
                 }
             }
+        } else if (idx->row_type != KNHIP_ROWTYPE_FP32) { // rows kept narrow: widened (exact) to the fp32 bytes the host sees
+            DevBuf wide;
+            HIP_TRY(wide.alloc(b));
+            HIP_TRY(launch_rows_widen(idx->codes_aos.as<uint16_t>(), idx->ntotal * idx->d, idx->row_type, wide.as<float>(), nullptr));
+            HIP_TRY(hipMemcpy(codes, wide.p, b, hipMemcpyDeviceToHost));
         } else {
             HIP_TRY(hipMemcpy(codes, idx->codes_aos.p, b, hipMemcpyDeviceToHost));
         }

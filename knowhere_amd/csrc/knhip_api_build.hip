@@ -318,12 +318,20 @@ int add_device_impl(knhip_index* idx, int64_t n, const float* d_x, const int64_t
     }
     if (int rc = check_trained_for_add(idx)) return rc;
     const int64_t nlist = idx->nlist;
-    const int64_t cs = idx->code_size;
+    const int64_t cs = idx->dev_code_size();
     const int64_t n0 = idx->has_data ? idx->ntotal : 0;
     DevBuf assign, codes, ids_new, sorted_rows, seg_off, tmp;
     HIP_TRY(assign.alloc((size_t)n * sizeof(int64_t)));
-    HIP_TRY(codes.alloc((size_t)n * cs));
-    if (int rc = encode_rows(idx, n, d_x, assign.as<int64_t>(), codes.as<uint8_t>(), nullptr, d_x_assign)) return rc;
+    if (idx->row_type != KNHIP_ROWTYPE_FP32) {
+        // IVF_FLAT rows kept narrow: checked and narrowed before anything is merged (a refused batch leaves the index as
+        // it was); the assignment is taken from the fp32 rows, which hold the same values
+        if (int rc = narrow_rows(idx, n, d_x, codes, "add")) return rc;
+        if (int rc = assign_rows(idx, d_x_assign ? d_x_assign : d_x, n, assign.as<int64_t>(), nullptr)) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    } else {
+        HIP_TRY(codes.alloc((size_t)n * cs));
+        if (int rc = encode_rows(idx, n, d_x, assign.as<int64_t>(), codes.as<uint8_t>(), nullptr, d_x_assign)) return rc;
+    }
     const int64_t* new_ids = d_ids;
     if (!d_ids) { // Knowhere ids are the running row numbers (IvfIndexNode::Add -> add_core without xids)
         HIP_TRY(ids_new.alloc((size_t)n * sizeof(int64_t)));
@@ -495,6 +503,33 @@ int knhip_index_add_device(knhip_index* idx, int64_t n, const float* d_x, const 
     return add_device_impl(idx, n, d_x, d_ids);
 }
 
+} // extern "C"
+
+namespace knhip_host {
+// A host Add of several slices on a typed IVF_FLAT index: every value is checked BEFORE the first slice is merged (each
+// slice's own device check would only see its slice, and a refusal in a later one would leave the earlier ones stored).
+// The rows named are the caller's.
+static int check_host_rows(const knhip_index* idx, int64_t n, const float* x, const char* who) {
+    if (idx->row_type == KNHIP_ROWTYPE_FP32) {
+        return KNHIP_OK;
+    }
+    const uint32_t* u = reinterpret_cast<const uint32_t*>(x);
+    const int64_t nval = n * idx->d;
+    for (int64_t t = 0; t < nval; t++) {
+        uint32_t h;
+        if (!row_narrow(u[t], idx->row_type, &h)) {
+            const char* tname = idx->row_type == KNHIP_ROWTYPE_BF16 ? "bf16" : "fp16";
+            return fail(KNHIP_ERR_INVALID_ARGS, std::string(who) + ": row_type " + tname + " cannot hold the value at row " +
+                                                        std::to_string(t / idx->d) + ", dimension " + std::to_string(t % idx->d) +
+                                                        " exactly (nothing is rounded; the index is unchanged)");
+        }
+    }
+    return KNHIP_OK;
+}
+} // namespace knhip_host
+
+extern "C" {
+
 int knhip_index_add(knhip_index* idx, int64_t n, const float* x, const int64_t* ids) {
     if (int rc = check_index(idx)) return rc;
     if (n < 0 || (n > 0 && !x)) {
@@ -503,7 +538,7 @@ int knhip_index_add(knhip_index* idx, int64_t n, const float* x, const int64_t* 
     DeviceGuard g(idx->desc.device);
     std::lock_guard<std::mutex> lk(idx->add_mu);
     // slices of at most 1 GiB of rows keep the staging buffer bounded
-    const int64_t step = std::max<int64_t>(1, ((int64_t)1 << 30) / ((int64_t)idx->d * 4));
+    const int64_t step = env_add_slice_rows(idx->d);
     if (idx->desc.kind == KNHIP_BRUTE_FORCE || n <= step) {
         DevBuf dx, di;
         if (int rc = upload(dx, x, (size_t)n * idx->d * sizeof(float))) return rc;
@@ -512,6 +547,7 @@ int knhip_index_add(knhip_index* idx, int64_t n, const float* x, const int64_t* 
         }
         return add_device_impl(idx, n, dx.as<float>(), ids ? di.as<int64_t>() : nullptr);
     }
+    if (int rc = check_host_rows(idx, n, x, "add")) return rc;
     for (int64_t i0 = 0; i0 < n; i0 += step) {
         const int64_t m = std::min(step, n - i0);
         DevBuf dx, di;
@@ -536,7 +572,10 @@ int knhip_index_add_assigned_by(knhip_index* idx, int64_t n, const float* x_stor
     DeviceGuard g(idx->desc.device);
     std::lock_guard<std::mutex> lk(idx->add_mu);
     // slices of at most 1 GiB per row array keep the staging buffers bounded, as knhip_index_add does
-    const int64_t step = std::max<int64_t>(1, ((int64_t)1 << 30) / ((int64_t)idx->d * 4));
+    const int64_t step = env_add_slice_rows(idx->d);
+    if (n > step) {
+        if (int rc = check_host_rows(idx, n, x_store, "add_assigned_by")) return rc;
+    }
     for (int64_t i0 = 0; i0 < n; i0 += step) {
         const int64_t m = std::min(step, n - i0);
         DevBuf dx, da, di;

@@ -110,6 +110,7 @@ IterScanArgs scan_args(const knhip_iter* it) {
     a.centroids = idx->centroids.as<float>();
     a.trained = idx->sq_trained.as<float>();
     a.sq_bits = idx->sq_bits;
+    a.row_type = idx->row_type;
     a.row_scale = idx->row_scale.as<float>();
     a.cos_mode = idx->cos_mode;
     a.id_desc = it->id_desc;

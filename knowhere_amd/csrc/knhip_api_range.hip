@@ -51,7 +51,8 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
         fc.nrows = ncol;
         fc.chunk_rows = std::max<int64_t>(1024, round_up((ncol + 1023) / 1024, 64));
         fc.d = d;
-        fc.nchunk = (d + 3) / 4;
+        fc.nchunk = row_nchunk(d, idx->row_type);
+        fc.row_type = idx->row_type;
         fc.queries = d_q;
         fc.nq = nq;
         fc.row_scale = idx->row_scale.as<float>();
@@ -123,7 +124,7 @@ static int range_batch(const knhip_index* idx, Workspace* ws, const float* d_q, 
             // (one or two queries -- the boundary rule's flagged ones --: one item per pair instead of the grouped table)
             HIP_TRY(launch_direct_items(keys_w, nq, W, nlist, idx->d_list_len.as<int64_t>(), wt, s));
         } else {
-            HIP_TRY(launch_build_worktable(keys_w, nq, W, nlist, qg, qg, idx->d_list_len.as<int64_t>(), idx->code_size, wt, s));
+            HIP_TRY(launch_build_worktable(keys_w, nq, W, nlist, qg, qg, idx->d_list_len.as<int64_t>(), idx->dev_code_size(), wt, s));
         }
         // (dump mode: k = 1, no partial lists)
         const Batch in{d_q, nq, 1, W, d_bitset, nbits, nullptr, nullptr, keys_w, cdis_w};

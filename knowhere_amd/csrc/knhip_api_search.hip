@@ -45,7 +45,8 @@ FlatScanArgs flat_scan_args(const knhip_index* idx, const Workspace* ws, const B
     FlatScanArgs a = item_scan_args<FlatScanArgs>(idx, ws, b, wt);
     a.rows = idx->rows.as<float4>();
     a.list_blk_off = idx->d_list_blk_off.as<int64_t>();
-    a.nchunk = (idx->d + 3) / 4;
+    a.nchunk = row_nchunk(idx->d, idx->row_type);
+    a.row_type = idx->row_type;
     a.nq = b.nq;
     a.row_scale = idx->row_scale.as<float>();
     a.cos_mode = idx->cos_mode;
@@ -192,8 +193,8 @@ SearchPlan plan_search(const knhip_index* idx, int64_t nq, int k, int nprobe, bo
             p.ms_nchunk = d / 4;
             lds = pqf_smem();
         } else if (kind == KNHIP_IVF_FLAT) {
-            p.ms_nchunk = (d + 3) / 4;
-            p.ms_nstep = (p.ms_nchunk + 3) / 4;
+            p.ms_nchunk = row_nchunk(d, idx->row_type);
+            p.ms_nstep = (d + 15) / 16; // (steps of 16 dims: four fp32 chunks, two typed ones)
             lds = mscan_flat_smem(p.ms_nstep);
         } else {
             const int step_chunks = idx->sq_bits == 6 ? 3 : 2; // (sq_codec.h SqStep: 32 dims for 8 bits, 64 for 6 and 4)
@@ -383,7 +384,7 @@ int build_worktable(const knhip_index* idx, Workspace* ws, const SearchPlan& pla
         cls = ws->ms_sample_off.as<int32_t>();
     }
     HIP_TRY(launch_build_worktable(b.keys, b.nq, b.nprobe, idx->nlist, plan.qg_rank0, plan.qg_bulk, idx->d_list_len.as<int64_t>(),
-                                   idx->code_size, wt, s, 0, cls));
+                                   idx->dev_code_size(), wt, s, 0, cls));
     return KNHIP_OK;
 }
 
@@ -509,6 +510,7 @@ int ms_common_args(const knhip_index* idx, Workspace* ws, const SearchPlan& plan
     m.nchunk = plan.ms_nchunk;
     m.nstep = plan.ms_nstep;
     m.sq_bits = kind == KNHIP_IVF_SQ8 ? idx->sq_bits : 0;
+    m.row_type = idx->row_type;
     m.queries = b.q;
     m.qnorm = ws->qnorm.as<float>();
     m.coarse_dis = b.cdis;
@@ -570,7 +572,7 @@ int ms_fork_group(const knhip_index* idx, Workspace* ws, const SearchPlan& plan,
     HIP_TRY(hipEventRecord(ws->ev_fork, s));
     HIP_TRY(hipStreamWaitEvent(ws->side, ws->ev_fork, 0));
     HIP_TRY(launch_build_worktable(b.keys, b.nq, b.nprobe, idx->nlist, plan.qg, plan.qg, idx->d_list_len.as<int64_t>(),
-                                   idx->code_size, *wside, ws->side, /*rank0_slot=*/-1));
+                                   idx->dev_code_size(), *wside, ws->side, /*rank0_slot=*/-1));
     HIP_TRY(hipEventRecord(ws->ev_join, ws->side));
     sj->forked = true;
     return KNHIP_OK;
@@ -630,7 +632,7 @@ int ms_sample_pass(const knhip_index* idx, Workspace* ws, const SearchPlan& plan
         return KNHIP_OK;
     }
     HIP_TRY(launch_ms_units(wt.list_count, wt.list_pair_off, nlist, plan.ms_qt0, ws->ms_unit_off.as<int64_t>(),
-                            ws->ms_nunits.as<int64_t>(), ws->ms_units.as<KnItem>(), idx->d_list_len.as<int64_t>(), idx->code_size,
+                            ws->ms_nunits.as<int64_t>(), ws->ms_units.as<KnItem>(), idx->d_list_len.as<int64_t>(), idx->dev_code_size(),
                             nullptr, s));
     ds.sample_off = ws->ms_sample_off.as<int32_t>();
     HIP_TRY(launch_filter(idx, plan, PqForm{}, ds, plan.ms_bound0, s));
@@ -810,11 +812,11 @@ int ms_group_units(const knhip_index* idx, Workspace* ws, const SearchPlan& plan
         if (int rc = sj->join()) return rc;
     } else {
         HIP_TRY(launch_build_worktable(b.keys, b.nq, b.nprobe, nlist, plan.qg, plan.qg, idx->d_list_len.as<int64_t>(),
-                                       idx->code_size, wside, s, /*rank0_slot=*/-1));
+                                       idx->dev_code_size(), wside, s, /*rank0_slot=*/-1));
     }
     m.pairs = wside.pairs;
     HIP_TRY(launch_ms_units(wside.list_count + nlist, wside.list_pair_off + nlist, nlist, f.qt, ws->ms_unit_off.as<int64_t>(),
-                            ws->ms_nunits.as<int64_t>(), ws->ms_units.as<KnItem>(), idx->d_list_len.as<int64_t>(), idx->code_size,
+                            ws->ms_nunits.as<int64_t>(), ws->ms_units.as<KnItem>(), idx->d_list_len.as<int64_t>(), idx->dev_code_size(),
                             idx->scan_bytes_dev.as<double>() + 2, s, f.pqd_cost, ws->pqd_tiles.as<int2>()));
     return KNHIP_OK;
 }

@@ -81,6 +81,16 @@ inline EnvLayout env_layout() {
     return e;
 }
 
+// KNHIP_ADD_SLICE_ROWS=n: rows per staging slice of the host Add entry points (default: 1 GiB of fp32 rows); tests force
+// several slices with a small batch.  Read by every host Add.
+inline long long env_add_slice_rows(int d) {
+    const char* v = std::getenv("KNHIP_ADD_SLICE_ROWS");
+    if (v && *v && std::atoll(v) > 0) {
+        return std::atoll(v);
+    }
+    return std::max<long long>(1, ((long long)1 << 30) / ((long long)d * 4));
+}
+
 inline EnvSearch env_search() {
     EnvSearch e{};
     const char* a = std::getenv("KNHIP_MS_SAMPLE_ROWS");

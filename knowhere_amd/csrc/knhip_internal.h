@@ -228,6 +228,9 @@ struct knhip_index {
     int64_t ntotal = 0;
     int64_t code_size = 0;
     int sq_bits = 8;      // IVF_SQ8: code width (sq_type SQ8 / SQ6 / SQ4); code_size = sq_code_size(d, sq_bits)
+    int row_type = 0;     // IVF_FLAT: KNHIP_ROWTYPE_* of the resident rows (`rows`, `codes_aos`); code_size stays 4 d (the host's view)
+    // bytes of one row in the resident copies
+    int64_t dev_code_size() const { return row_type != 0 ? 2 * (int64_t)d : code_size; }
     int64_t id_offset = 0;
     std::vector<int64_t> h_list_len, h_list_row_off;
     DevBuf d_list_len, d_list_row_off, d_list_blk_off;
@@ -380,7 +383,11 @@ inline int upload(DevBuf& dst, const void* src, size_t bytes) {
 int coarse_stage(const knhip_index* idx, Workspace* ws, const float* d_q, int64_t nq, int nprobe, int64_t* keys, float* cdis,
                  hipStream_t s);
 int maybe_build_precomp(knhip_index* idx);
+// d_codes: rows of idx->dev_code_size() bytes (a typed IVF_FLAT index: already narrowed, see narrow_rows)
 int build_list_layout(knhip_index* idx, const std::vector<int64_t>& list_off, const uint8_t* d_codes, const int64_t* d_ids);
+// typed IVF_FLAT: n fp32 rows -> n rows of 2 d bytes in `out`, or KNHIP_ERR_INVALID_ARGS naming the first value the type
+// cannot hold (nothing of the index is touched)
+int narrow_rows(const knhip_index* idx, int64_t n, const float* d_x, DevBuf& out, const char* who);
 int ensure_aos(const knhip_index* cidx);
 Workspace* acquire_ws(const knhip_index* idx, void* stream_key, bool pooled_by_stream);
 void release_ws(const knhip_index* idx, Workspace* w);

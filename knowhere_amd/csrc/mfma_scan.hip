@@ -57,6 +57,8 @@ constexpr int MS_QT = 32 * MS_NQT; // queries per unit
 constexpr int MS_SAMPLE = 8192;    // rows that feed tau_q, at most (a multiple of 64, <= row_select's limit)
 
 // ---- ||x||^2 per stored row position (padded block layout), and the maximum ----------------------------------
+// (RT: rows kept as fp16 / bf16 -- chunks of 8 dims, widened; the sum takes the fp32 kernel's order, four dims at a time)
+template <int RT = KN_ROW_FP32>
 __global__ void ms_block_norms_kernel(const float4* __restrict__ rows, int64_t total_blk, int nchunk,
                                       float* __restrict__ out, float* __restrict__ out_max) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -65,9 +67,18 @@ __global__ void ms_block_norms_kernel(const float4* __restrict__ rows, int64_t t
         const int64_t b = t >> 6;
         const int r = (int)(t & 63);
         const float4* p = rows + b * (int64_t)nchunk * 64 + r;
-        for (int c = 0; c < nchunk; c++) {
-            const float4 v = p[(int64_t)c * 64];
-            acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+        if constexpr (RT != KN_ROW_FP32) {
+            for (int c = 0; c < nchunk; c++) {
+                float v[8];
+                row_widen8<RT>(reinterpret_cast<const uint4*>(p)[(int64_t)c * 64], v);
+                acc += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+                acc += v[4] * v[4] + v[5] * v[5] + v[6] * v[6] + v[7] * v[7];
+            }
+        } else {
+            for (int c = 0; c < nchunk; c++) {
+                const float4 v = p[(int64_t)c * 64];
+                acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+            }
         }
         out[t] = acc;
     }
@@ -82,12 +93,14 @@ __global__ void ms_block_norms_kernel(const float4* __restrict__ rows, int64_t t
 }
 
 hipError_t launch_ms_block_norms(const float4* rows, int64_t total_blk, int nchunk, float* out, float* out_max,
-                                 hipStream_t s) {
+                                 hipStream_t s, int row_type) {
     hipError_t e = hipMemsetAsync(out_max, 0, sizeof(float), s);
     if (e != hipSuccess || total_blk <= 0) {
         return e;
     }
-    hipLaunchKernelGGL(ms_block_norms_kernel, dim3((unsigned)((total_blk * 64 + 255) / 256)), dim3(256), 0, s, rows,
+    auto kern = row_type == KN_ROW_FP16 ? ms_block_norms_kernel<KN_ROW_FP16>
+              : row_type == KN_ROW_BF16 ? ms_block_norms_kernel<KN_ROW_BF16> : ms_block_norms_kernel<KN_ROW_FP32>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((total_blk * 64 + 255) / 256)), dim3(256), 0, s, rows,
                        total_blk, nchunk, out, out_max);
     return hipGetLastError();
 }
@@ -225,7 +238,20 @@ hipError_t launch_ms_units(const int32_t* list_count_v, const int64_t* list_pair
 // Per-pair constant in LDS (sT): filter: the accumulator threshold t; dump: c with value = c - 2 acc (L2: c = ||q||^2
 // + eps) or value = acc - c (IP: c = eps).
 // NQT = query tiles of 32 per unit (2 in filter mode; 1 in the sample pass, whose units hold few queries).
-template <bool IS_L2, bool DUMP, int NQT>
+// RT: element type of the rows.  Typed rows (chunks of 8 dims): both half-waves load the chunk of their 8-dim slab (the
+// same 512 bytes: one fetch) and each widens its own four values -- exact, so the products are the fp32 rows' products.
+template <int RT>
+__device__ __forceinline__ float4 ms_row_operand(const float4& v, int hi) {
+    if constexpr (RT == KN_ROW_FP32) {
+        return v;
+    } else {
+        const uint32_t w0 = __float_as_uint(hi ? v.z : v.x), w1 = __float_as_uint(hi ? v.w : v.y); // (bit moves only)
+        return make_float4(row_widen<RT>(w0 & 0xffffu), row_widen<RT>(w0 >> 16), row_widen<RT>(w1 & 0xffffu),
+                           row_widen<RT>(w1 >> 16));
+    }
+}
+
+template <bool IS_L2, bool DUMP, int NQT, int RT = KN_ROW_FP32>
 __device__ __forceinline__ void mscan_flat_unit(const MScanArgs a, const int64_t u, unsigned char* smem) {
     constexpr int QT = 32 * NQT;
     const int lane = lane_id();
@@ -312,7 +338,7 @@ __device__ __forceinline__ void mscan_flat_unit(const MScanArgs a, const int64_t
         const int64_t bb = min(b, nblk - 1);
 #pragma unroll
         for (int sl = 0; sl < 2; sl++) {
-            const int c = min(4 * s + 2 * sl + hi, nchunk - 1);
+            const int c = RT == KN_ROW_FP32 ? min(4 * s + 2 * sl + hi, nchunk - 1) : min(2 * s + sl, nchunk - 1);
             const float4* p = rows + (bb * nchunk + c) * 64 + lr;
             A[0][sl] = p[0];
             A[1][sl] = p[32];
@@ -364,14 +390,15 @@ __device__ __forceinline__ void mscan_flat_unit(const MScanArgs a, const int64_t
             for (int qt = 0; qt < NQT; qt++) {
                 B[qt] = *reinterpret_cast<const float4*>(sQ + (qt * 32 + lr) * ldq + (2 * s + sl) * 8 + 4 * hi);
             }
+            const float4 Av[2] = {ms_row_operand<RT>(Ac[0][sl], hi), ms_row_operand<RT>(Ac[1][sl], hi)};
 #pragma unroll
             for (int qt = 0; qt < NQT; qt++) {
 #pragma unroll
                 for (int t = 0; t < 2; t++) {
-                    acc[t][qt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ac[t][sl].x, B[qt].x, acc[t][qt], 0, 0, 0);
-                    acc[t][qt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ac[t][sl].y, B[qt].y, acc[t][qt], 0, 0, 0);
-                    acc[t][qt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ac[t][sl].z, B[qt].z, acc[t][qt], 0, 0, 0);
-                    acc[t][qt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ac[t][sl].w, B[qt].w, acc[t][qt], 0, 0, 0);
+                    acc[t][qt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Av[t].x, B[qt].x, acc[t][qt], 0, 0, 0);
+                    acc[t][qt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Av[t].y, B[qt].y, acc[t][qt], 0, 0, 0);
+                    acc[t][qt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Av[t].z, B[qt].z, acc[t][qt], 0, 0, 0);
+                    acc[t][qt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Av[t].w, B[qt].w, acc[t][qt], 0, 0, 0);
                 }
             }
         }
@@ -457,13 +484,13 @@ __device__ __forceinline__ void mscan_flat_unit(const MScanArgs a, const int64_t
 
 // One unit per workgroup in XCD-aware order; a.unit_loop: a fixed grid walks a unit table whose size only the device
 // knows (the retry round of overflowed queries).  Every exit inside a unit is workgroup-uniform.
-template <bool IS_L2, bool DUMP, int NQT, bool LOOP>
+template <bool IS_L2, bool DUMP, int NQT, bool LOOP, int RT = KN_ROW_FP32>
 __global__ __launch_bounds__(MS_THREADS, 4) void mscan_flat_kernel(MScanArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int64_t nunits = *a.nunits_dev;
     if (LOOP) {
         for (int64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
-            mscan_flat_unit<IS_L2, DUMP, NQT>(a, u, smem);
+            mscan_flat_unit<IS_L2, DUMP, NQT, RT>(a, u, smem);
             __syncthreads();
         }
     } else {
@@ -474,7 +501,7 @@ __global__ __launch_bounds__(MS_THREADS, 4) void mscan_flat_kernel(MScanArgs a) 
         if (u >= nunits) {
             return;
         }
-        mscan_flat_unit<IS_L2, DUMP, NQT>(a, u, smem);
+        mscan_flat_unit<IS_L2, DUMP, NQT, RT>(a, u, smem);
     }
 }
 
@@ -1139,7 +1166,7 @@ constexpr int MF_THREADS = 256;
 constexpr int MF_MLP = 8; // row pieces requested at a time per candidate
 
 // KIND 1: fp32 rows, 2: PQ codes (M = 32, dsub = 4; pq_filter.hip), 3: IVF-SQ codes of BITS bits
-template <bool IS_L2, int KIND, int BITS = 8>
+template <bool IS_L2, int KIND, int BITS = 8, int RT = KN_ROW_FP32>
 __global__ __launch_bounds__(MF_THREADS) void mscan_finish_kernel(MScanArgs a, const int64_t* __restrict__ keys,
                                                                   const float* __restrict__ coarse_dis, int nprobe,
                                                                   int k, int P_max, float* __restrict__ out_d,
@@ -1363,7 +1390,7 @@ __global__ __launch_bounds__(MF_THREADS) void mscan_finish_kernel(MScanArgs a, c
     float* sq = reinterpret_cast<float*>(smem + (size_t)P_max * 12);
     using SW = SqWidth<BITS>;
     const int sq_ngroup = (a.nchunk + SW::GROUP_CHUNKS - 1) / SW::GROUP_CHUNKS;
-    const int dq = KIND == 3 ? sq_ngroup * SW::GROUP_DIMS : a.nchunk * 4;
+    const int dq = KIND == 3 ? sq_ngroup * SW::GROUP_DIMS : a.nchunk * (RT == KN_ROW_FP32 ? 4 : 8);
     float* svmin = sq + dq;
     float* svdiff = svmin + dq;
     for (int i = tid; i < dq; i += MF_THREADS) {
@@ -1396,7 +1423,22 @@ __global__ __launch_bounds__(MF_THREADS) void mscan_finish_kernel(MScanArgs a, c
                 float acc = 0.f;
                 // A candidate's row is gathered in 16-byte pieces 1 KiB apart (interleaved blocks): MF_MLP of them are
                 // requested at a time -- one dependent load per piece made this stage latency-bound (C5: 25 ms).
-                if (KIND == 1) {
+                if constexpr (KIND == 1 && RT != KN_ROW_FP32) { // rows kept as fp16 / bf16: widened, then the steps below
+                    const uint4* p = reinterpret_cast<const uint4*>(a.rows) + blk * (int64_t)a.nchunk * 64 + r;
+                    for (int c0 = 0; c0 < a.nchunk; c0 += MF_MLP) {
+                        uint4 yy[MF_MLP];
+#pragma unroll
+                        for (int u = 0; u < MF_MLP; u++) {
+                            yy[u] = p[(int64_t)min(c0 + u, a.nchunk - 1) * 64];
+                        }
+#pragma unroll
+                        for (int u = 0; u < MF_MLP; u++) {
+                            if (c0 + u < a.nchunk) {
+                                acc = row_chunk8_steps<IS_L2, RT>(acc, yy[u], sq + (c0 + u) * 8);
+                            }
+                        }
+                    }
+                } else if (KIND == 1) {
                     const float4* p = reinterpret_cast<const float4*>(a.rows) + blk * (int64_t)a.nchunk * 64 + r;
                     for (int c0 = 0; c0 < a.nchunk; c0 += MF_MLP) {
                         float4 yy[MF_MLP];
@@ -1706,17 +1748,25 @@ int mscan_sample_rows() {
     return MS_SAMPLE;
 }
 
+template <int RT>
+static auto mscan_flat_pick(bool is_l2, bool dump, bool loop) {
+    auto kern = is_l2 ? (dump ? mscan_flat_kernel<true, true, 1, false, RT> : mscan_flat_kernel<true, false, MS_NQT, false, RT>)
+                      : (dump ? mscan_flat_kernel<false, true, 1, false, RT> : mscan_flat_kernel<false, false, MS_NQT, false, RT>);
+    if (loop && !dump) { // the retry round's one-query units
+        kern = is_l2 ? mscan_flat_kernel<true, false, MS_NQT, true, RT> : mscan_flat_kernel<false, false, MS_NQT, true, RT>;
+    }
+    return kern;
+}
+
 hipError_t launch_mscan_flat(const MScanArgs& a, bool is_l2, int64_t units_bound, hipStream_t s) {
     if (units_bound <= 0) {
         return hipSuccess;
     }
     const bool dump = a.dump != nullptr;
     const size_t sm = dump ? (size_t)32 * (a.nstep * 16 + 4) * 4 + (size_t)32 * 16 : mscan_flat_smem(a.nstep);
-    auto kern = is_l2 ? (dump ? mscan_flat_kernel<true, true, 1, false> : mscan_flat_kernel<true, false, MS_NQT, false>)
-                      : (dump ? mscan_flat_kernel<false, true, 1, false> : mscan_flat_kernel<false, false, MS_NQT, false>);
-    if (a.unit_loop && !dump) { // the retry round's one-query units
-        kern = is_l2 ? mscan_flat_kernel<true, false, MS_NQT, true> : mscan_flat_kernel<false, false, MS_NQT, true>;
-    }
+    auto kern = a.row_type == KN_ROW_FP16 ? mscan_flat_pick<KN_ROW_FP16>(is_l2, dump, a.unit_loop != 0)
+              : a.row_type == KN_ROW_BF16 ? mscan_flat_pick<KN_ROW_BF16>(is_l2, dump, a.unit_loop != 0)
+                                          : mscan_flat_pick<KN_ROW_FP32>(is_l2, dump, a.unit_loop != 0);
     if (sm > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
@@ -1750,7 +1800,7 @@ hipError_t launch_mscan_finish(const MScanArgs& a, int kind, bool is_l2, const i
     if (kind == 3 && !sq_bits_valid(bits)) {
         return hipErrorInvalidValue;
     }
-    const int dq = kind == 3 ? sq_dpad(a.d, bits) : a.nchunk * 4;
+    const int dq = kind == 3 ? sq_dpad(a.d, bits) : a.nchunk * (kind == 1 ? row_chunk_dims(a.row_type) : 4);
     const size_t sm = (size_t)P_max * 12 + (size_t)dq * 4 * (kind == 3 ? 3 : 1);
 #define MF_LAUNCH(L2_, KIND_, ...)                                                                              \
     do {                                                                                                        \
@@ -1763,7 +1813,11 @@ hipError_t launch_mscan_finish(const MScanArgs& a, int kind, bool is_l2, const i
         hipLaunchKernelGGL(kern, dim3((unsigned)a.nq), dim3(MF_THREADS), sm, s, a, keys, coarse_dis, nprobe, k, \
                            P_max, out_d, out_i, counters, pass);                                                \
     } while (0)
-    if (kind == 1) {
+    if (kind == 1 && a.row_type == KN_ROW_FP16) {
+        if (is_l2) MF_LAUNCH(true, 1, 8, KN_ROW_FP16); else MF_LAUNCH(false, 1, 8, KN_ROW_FP16);
+    } else if (kind == 1 && a.row_type == KN_ROW_BF16) {
+        if (is_l2) MF_LAUNCH(true, 1, 8, KN_ROW_BF16); else MF_LAUNCH(false, 1, 8, KN_ROW_BF16);
+    } else if (kind == 1) {
         if (is_l2) MF_LAUNCH(true, 1); else MF_LAUNCH(false, 1);
     } else if (kind == 2) {
         if (is_l2) MF_LAUNCH(true, 2); else MF_LAUNCH(false, 2);

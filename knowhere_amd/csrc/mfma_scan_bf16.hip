@@ -19,6 +19,14 @@
 // shifts, two subtractions per pair of values -- issued beside the matrix instructions of the previous step); the queries
 // are split once per unit into LDS.
 //
+// Typed rows (knhip_index_set_row_type: the lists kept as fp16 / bf16, 16-byte chunks of 8 dimensions).  A half-wave reads
+// 32 rows x ONE chunk per step -- the same lane share of the A operand at half the bytes.  bf16 rows: the loaded chunk IS
+// the hi operand, lo_x = 0 and r_x = 0, so the lo_q hi_x + hi_q hi_x pair is the whole product and the hi_q lo_x
+// instruction is dropped: two matrix instructions per step and no conversion.  fp16 rows: hi = bf16(x) by round to nearest,
+// lo = x - hi is exact in bf16 (x has 11 significant bits, hi takes 8: the remainder has at most 3 and its exponent lies
+// within bf16's, which is fp32's) so r_x = 0; three instructions as for fp32 rows.  In both cases the dropped terms are a
+// subset of lo lo + r_q x + q r_x: the bound above and the caller's eps_scale stay valid upper bounds and are kept.
+//
 // Reference semantics replaced: as mscan_flat_kernel (IVFFlatScanner::scan_codes, thirdparty/faiss/faiss/cppcontrib/
 // knowhere/IndexIVFFlat.cpp:193-236) -- only WHICH rows reach the exact finish, never a returned value.
 #include "common.h"
@@ -30,6 +38,7 @@ namespace knhip {
 typedef float mb_f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 mb_bf8 __attribute__((ext_vector_type(8)));
 typedef __bf16 mb_bf4 __attribute__((ext_vector_type(4)));
+typedef uint32_t mb_u4 __attribute__((ext_vector_type(4)));
 
 constexpr int MB_WAVES = 4;
 constexpr int MB_THREADS = MB_WAVES * KN_WAVE;
@@ -51,7 +60,25 @@ __device__ __forceinline__ void mb_split8(const float4& f0, const float4& f1, mb
     }
 }
 
-template <bool IS_L2, int NQT>
+// a chunk of 8 fp16 values -> the split operands (lo exact: see the header)
+__device__ __forceinline__ void mb_split8_f16(const float4& f, mb_bf8& hi, mb_bf8& lo) {
+    float v[8];
+    row_widen8<KN_ROW_FP16>(make_uint4(__float_as_uint(f.x), __float_as_uint(f.y), __float_as_uint(f.z), __float_as_uint(f.w)), v);
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+        const __bf16 h = (__bf16)v[e];
+        hi[e] = h;
+        lo[e] = (__bf16)(v[e] - (float)h);
+    }
+}
+// a chunk of 8 bf16 values: the operand as it lies in memory
+__device__ __forceinline__ mb_bf8 mb_as_bf8(const float4& f) {
+    const mb_u4 w = {__float_as_uint(f.x), __float_as_uint(f.y), __float_as_uint(f.z), __float_as_uint(f.w)};
+    return __builtin_bit_cast(mb_bf8, w);
+}
+
+// RT: element type of the rows (kernels.h KN_ROW_*); NE = 16-byte loads per lane, tile and step
+template <bool IS_L2, int NQT, int RT = KN_ROW_FP32>
 __device__ __forceinline__ void mscan_flatb_unit(const MScanArgs a, const int64_t u, unsigned char* smem) {
     constexpr int QT = 32 * NQT;
     const int lane = lane_id();
@@ -64,8 +91,9 @@ __device__ __forceinline__ void mscan_flatb_unit(const MScanArgs a, const int64_
     const int64_t blk0 = a.list_blk_off[list];
     const int64_t row_off = a.list_row_off[list];
     const int nchunk = a.nchunk;
-    const int nstep = a.nstep; // steps of 16 dims (4 chunks)
+    const int nstep = a.nstep; // steps of 16 dims (4 chunks; typed rows: 2)
     const int pitch = mb_pitch(nstep);
+    constexpr int NE = RT == KN_ROW_FP32 ? 2 : 1;
 
     unsigned char* sQ = smem;                                        // [QT][pitch]
     float* sT = reinterpret_cast<float*>(smem + (size_t)QT * pitch); // [QT] accumulator threshold
@@ -153,20 +181,21 @@ __device__ __forceinline__ void mscan_flatb_unit(const MScanArgs a, const int64_
     // A operand of one step (16 dims): lane (row lr of tile t, half hi) takes chunks 4 s + 2 hi and + 1 = its 8 dims.
     // Branch-free as in mscan_flat_kernel: a prefetch past this wave's last block re-reads that block (never used); a chunk
     // past the last one re-reads the last chunk, whose query operand is zero in LDS.
-    auto load_step = [&](int64_t b, int s, float4 (&A)[2][2]) {
+    // Typed rows: the lane's 8 dims are ONE chunk, 2 s + hi (the bits travel in a float4, untouched).
+    auto load_step = [&](int64_t b, int s, float4 (&A)[2][NE]) {
         const int64_t bb = min(b, nblk - 1);
 #pragma unroll
-        for (int e = 0; e < 2; e++) {
-            const int c = min(4 * s + 2 * hi + e, nchunk - 1);
+        for (int e = 0; e < NE; e++) {
+            const int c = RT == KN_ROW_FP32 ? min(4 * s + 2 * hi + e, nchunk - 1) : min(2 * s + hi, nchunk - 1);
             const float4* p = rows + (bb * nchunk + c) * 64 + lr;
             A[0][e] = p[0];
             A[1][e] = p[32];
         }
     };
-    float4 A[2][2][2]; // two statically rotating row buffers
+    float4 A[2][2][NE]; // two statically rotating row buffers
     int64_t lb = wave; // load cursor
     int ls = 0;
-    auto issue = [&](float4 (&dst)[2][2]) {
+    auto issue = [&](float4 (&dst)[2][NE]) {
         load_step(lb, ls, dst);
         if (++ls == nstep) {
             ls = 0;
@@ -198,11 +227,17 @@ __device__ __forceinline__ void mscan_flatb_unit(const MScanArgs a, const int64_
             acc[1][qt] = i1;
         }
     };
-    auto compute = [&](const float4 (&Ac)[2][2], int s) {
+    auto compute = [&](const float4 (&Ac)[2][NE], int s) {
         mb_bf8 ah[2], al[2];
 #pragma unroll
         for (int t = 0; t < 2; t++) {
-            mb_split8(Ac[t][0], Ac[t][1], ah[t], al[t]);
+            if constexpr (RT == KN_ROW_FP32) {
+                mb_split8(Ac[t][0], Ac[t][1], ah[t], al[t]);
+            } else if constexpr (RT == KN_ROW_FP16) {
+                mb_split8_f16(Ac[t][0], ah[t], al[t]);
+            } else {
+                ah[t] = mb_as_bf8(Ac[t][0]); // (lo_x = 0: no third instruction below)
+            }
         }
         const unsigned char* bq = sQ + (size_t)lr * pitch + s * 64 + hi * 16;
 #pragma unroll
@@ -214,7 +249,9 @@ __device__ __forceinline__ void mscan_flatb_unit(const MScanArgs a, const int64_
                 for (int t = 0; t < 2; t++) {
                     acc[t][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bh, acc[t][qt], 0, 0, 0);
                     acc[t][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bl, acc[t][qt], 0, 0, 0);
-                    acc[t][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t], bh, acc[t][qt], 0, 0, 0);
+                    if constexpr (RT != KN_ROW_BF16) {
+                        acc[t][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t], bh, acc[t][qt], 0, 0, 0);
+                    }
                 }
             }
         }
@@ -304,13 +341,13 @@ __device__ __forceinline__ void mscan_flatb_unit(const MScanArgs a, const int64_
 
 // One unit per workgroup in XCD-aware order; LOOP: a fixed grid walks a unit table whose size only the device knows (the
 // retry round of overflowed queries).  Every exit inside a unit is workgroup-uniform.
-template <bool IS_L2, int NQT, bool LOOP>
+template <bool IS_L2, int NQT, bool LOOP, int RT = KN_ROW_FP32>
 __global__ __launch_bounds__(MB_THREADS, 2) void mscan_flatb_kernel(MScanArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int64_t nunits = *a.nunits_dev;
     if (LOOP) {
         for (int64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
-            mscan_flatb_unit<IS_L2, NQT>(a, u, smem);
+            mscan_flatb_unit<IS_L2, NQT, RT>(a, u, smem);
             __syncthreads();
         }
     } else {
@@ -321,7 +358,7 @@ __global__ __launch_bounds__(MB_THREADS, 2) void mscan_flatb_kernel(MScanArgs a)
         if (u >= nunits) {
             return;
         }
-        mscan_flatb_unit<IS_L2, NQT>(a, u, smem);
+        mscan_flatb_unit<IS_L2, NQT, RT>(a, u, smem);
     }
 }
 
@@ -340,12 +377,20 @@ size_t mscan_flat_bf16_smem(int nstep) {
     return (size_t)qt * mb_pitch(nstep) + (size_t)qt * 16 + (size_t)MB_HITS * 16 + 16;
 }
 
+template <int NQT, int RT>
+static auto flatb_pick(bool is_l2, bool loop) {
+    auto kern = is_l2 ? mscan_flatb_kernel<true, NQT, false, RT> : mscan_flatb_kernel<false, NQT, false, RT>;
+    if (loop) { // the retry round's one-query units
+        kern = is_l2 ? mscan_flatb_kernel<true, NQT, true, RT> : mscan_flatb_kernel<false, NQT, true, RT>;
+    }
+    return kern;
+}
+
 template <int NQT>
 static hipError_t launch_flatb(const MScanArgs& a, bool is_l2, int64_t units_bound, size_t sm, hipStream_t s) {
-    auto kern = is_l2 ? mscan_flatb_kernel<true, NQT, false> : mscan_flatb_kernel<false, NQT, false>;
-    if (a.unit_loop) { // the retry round's one-query units
-        kern = is_l2 ? mscan_flatb_kernel<true, NQT, true> : mscan_flatb_kernel<false, NQT, true>;
-    }
+    auto kern = a.row_type == KN_ROW_FP16 ? flatb_pick<NQT, KN_ROW_FP16>(is_l2, a.unit_loop != 0)
+              : a.row_type == KN_ROW_BF16 ? flatb_pick<NQT, KN_ROW_BF16>(is_l2, a.unit_loop != 0)
+                                          : flatb_pick<NQT, KN_ROW_FP32>(is_l2, a.unit_loop != 0);
     if (sm > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);

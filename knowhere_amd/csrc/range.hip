@@ -128,7 +128,8 @@ __global__ void range_wave_state_kernel(const int32_t* __restrict__ cnt, int64_t
 
 // ---- IVF-Flat: exact distances of the wave's lists -> dist[q][column] (the arithmetic of flat_full_kernel, one
 // workgroup per (query, rank of the wave); column = padded position of the row in the interleaved store) --------------
-template <bool IS_L2>
+// RT: element type of the rows (typed rows widen in registers, the steps are the same).
+template <bool IS_L2, int RT = KN_ROW_FP32>
 __global__ __launch_bounds__(RG_THREADS) void range_flat_dump_kernel(FlatScanArgs a, const int64_t* __restrict__ keys_w,
                                                                      int W, int64_t nlist,
                                                                      const int64_t* __restrict__ seg_col,
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(RG_THREADS) void range_flat_dump_kernel(FlatScanArg
     const int64_t col0 = seg_col[key]; // (a multiple of 64: lists start on a block)
     // (compact dump of the large-k search: the pair's own first element instead of the list's column in the query's row)
     float* out = pair_col != nullptr ? dist + pair_col[blockIdx.x] : dist + q * ncol + col0;
-    const int dpad = a.nchunk * 4;
+    const int dpad = a.nchunk * (RT == KN_ROW_FP32 ? 4 : 8);
     float* sq = reinterpret_cast<float*>(smem);
     for (int i = threadIdx.x; i < dpad; i += RG_THREADS) {
         sq[i] = (i < a.d) ? a.queries[q * a.d + i] : 0.f;
@@ -161,20 +162,28 @@ __global__ __launch_bounds__(RG_THREADS) void range_flat_dump_kernel(FlatScanArg
         const int64_t row = b * 64 + lane;
         const float4* p = a.rows + (col0 / 64 + b) * (int64_t)a.nchunk * 64 + lane;
         float acc = 0.f;
+        if constexpr (RT != KN_ROW_FP32) {
+            const uint4* p16 = reinterpret_cast<const uint4*>(p);
 #pragma unroll 4
-        for (int c = 0; c < a.nchunk; c++) {
-            const float4 y = p[(int64_t)c * 64];
-            const float4 x = *reinterpret_cast<const float4*>(sq + c * 4);
-            if (IS_L2) {
-                acc = l2_step(acc, x.x, y.x);
-                acc = l2_step(acc, x.y, y.y);
-                acc = l2_step(acc, x.z, y.z);
-                acc = l2_step(acc, x.w, y.w);
-            } else {
-                acc = ip_step(acc, x.x, y.x);
-                acc = ip_step(acc, x.y, y.y);
-                acc = ip_step(acc, x.z, y.z);
-                acc = ip_step(acc, x.w, y.w);
+            for (int c = 0; c < a.nchunk; c++) {
+                acc = row_chunk8_steps<IS_L2, RT>(acc, p16[(int64_t)c * 64], sq + c * 8);
+            }
+        } else {
+#pragma unroll 4
+            for (int c = 0; c < a.nchunk; c++) {
+                const float4 y = p[(int64_t)c * 64];
+                const float4 x = *reinterpret_cast<const float4*>(sq + c * 4);
+                if (IS_L2) {
+                    acc = l2_step(acc, x.x, y.x);
+                    acc = l2_step(acc, x.y, y.y);
+                    acc = l2_step(acc, x.z, y.z);
+                    acc = l2_step(acc, x.w, y.w);
+                } else {
+                    acc = ip_step(acc, x.x, y.x);
+                    acc = ip_step(acc, x.y, y.y);
+                    acc = ip_step(acc, x.z, y.z);
+                    acc = ip_step(acc, x.w, y.w);
+                }
             }
         }
         if (row < len) {
@@ -393,8 +402,15 @@ hipError_t launch_range_flat_dump(const FlatScanArgs& a, const int64_t* keys_w, 
     if (nq <= 0 || W <= 0) {
         return hipSuccess;
     }
-    const size_t sm = (size_t)a.nchunk * 4 * sizeof(float);
+    const size_t sm = (size_t)a.nchunk * row_chunk_dims(a.row_type) * sizeof(float);
     auto kern = is_l2 ? range_flat_dump_kernel<true> : range_flat_dump_kernel<false>;
+    if (a.row_type == KN_ROW_FP16) {
+        kern = is_l2 ? range_flat_dump_kernel<true, KN_ROW_FP16> : range_flat_dump_kernel<false, KN_ROW_FP16>;
+    } else if (a.row_type == KN_ROW_BF16) {
+        kern = is_l2 ? range_flat_dump_kernel<true, KN_ROW_BF16> : range_flat_dump_kernel<false, KN_ROW_BF16>;
+    } else if (a.row_type != KN_ROW_FP32) {
+        return hipErrorInvalidValue;
+    }
     if (sm > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);

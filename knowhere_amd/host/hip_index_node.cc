@@ -305,7 +305,9 @@ class HipAnnIterator : public IndexNode::iterator {
 
 }  // namespace
 
-template <typename DataType, int Kind>
+// DefaultRowType: the row_type a config without the key gets (KNHIP_ROWTYPE_*; the fp16 / bf16 registrations of
+// GPU_HIP_IVF_FLAT keep such vectors as narrow on the device as they arrived)
+template <typename DataType, int Kind, int DefaultRowType = KNHIP_ROWTYPE_FP32>
 class HipIndexNode : public IndexNode {
     // (instantiated for fp16 / bf16 / int8 too, for the static registry entries -- StaticCreateConfig and friends, as
     // KNOWHERE_REGISTER_STATIC wants them --; an OBJECT exists for fp32 only: the other vector types come through the
@@ -417,6 +419,7 @@ class HipIndexNode : public IndexNode {
         }
         std::vector<int32_t> devs;
         if (Status st = SelectDevices(c, /*deserialize=*/false, &devs); st != Status::success) return st;
+        if (Status st = ReadRowType(c, devs); st != Status::success) return st;
         if (Status st = CreateShards(devs); st != Status::success) return st;
         if constexpr (Kind == KNHIP_BRUTE_FORCE) {
             return Status::success;  // nothing to train
@@ -504,6 +507,9 @@ class HipIndexNode : public IndexNode {
         };
         if (rc) {
             row_scale_by_id_.resize(scale0);
+            if (row_type_ != KNHIP_ROWTYPE_FP32 && rc == KNHIP_ERR_INVALID_ARGS) {
+                LOG_KNOWHERE_ERROR_ << TypeName() << ": Add: " << knhip_last_error();  // (names the row and the dimension)
+            }
             // one device, or a failure before anything was appended (assignment, routing): the index is unchanged
             if (W == 1 || CountLocked() == n0) return ToStatus(rc);
             return broken(ToStatus(rc));
@@ -1083,9 +1089,11 @@ class HipIndexNode : public IndexNode {
             if (c.metric_type.has_value() && IsMetricType(c.metric_type.value(), metric::COSINE) && new_metric == KNHIP_IP)
                 new_cosine = true;
             if (Status st = SelectDevices(c, /*deserialize=*/true, &devs); st != Status::success) return st;
+            if (Status st = ReadRowType(c, devs); st != Status::success) return st;
         } else {
             knowhere_config_type none;
             if (Status st = SelectDevices(none, /*deserialize=*/true, &devs); st != Status::success) return st;
+            if (Status st = ReadRowType(none, devs); st != Status::success) return st;
         }
         // The CPU cosine indexes keep the RAW rows plus their L2 norms (FLAT: the wire carries the norms, the index
         // multiplies by their inverses, L2NormsStorage::add_l2_norms IndexCosine.cpp:247-255; IVF_FLAT: ip / norm,
@@ -1172,7 +1180,12 @@ class HipIndexNode : public IndexNode {
                 cp[l] = x.codes[l].data();
                 ip[l] = x.ids[l].data();
             }
-            if ((rc = knhip_index_add_lists(h, sz.data(), cp.data(), ip.data()))) return bail(rc);
+            if ((rc = knhip_index_add_lists(h, sz.data(), cp.data(), ip.data()))) {
+                if (row_type_ != KNHIP_ROWTYPE_FP32 && rc == KNHIP_ERR_INVALID_ARGS) {
+                    LOG_KNOWHERE_ERROR_ << TypeName() << ": Deserialize: " << knhip_last_error();
+                }
+                return bail(rc);
+            }
         }
         if (StoredNormCosine()) {
             const Status st = PushRowScale();
@@ -1379,6 +1392,31 @@ class HipIndexNode : public IndexNode {
         return Status::success;
     }
 
+    // the row_type key (hip_index_node.h) -> row_type_, before the shards are created.  The names and the index type were
+    // checked by the config; here the default of this node type applies (a sharded index falls back to fp32 rows then) and
+    // a narrow type the caller NAMED is refused on a sharded index
+    Status
+    ReadRowType(const knowhere_config_type& c, const std::vector<int32_t>& devs) {
+        int32_t rt = DefaultRowType;
+        if (c.row_type.has_value()) rt = HipParseRowType(c.row_type.value());
+        if (rt < 0 || (rt != KNHIP_ROWTYPE_FP32 && Kind != KNHIP_IVF_FLAT)) {
+            LOG_KNOWHERE_ERROR_ << TypeName() << ": row_type " << c.row_type.value_or("") << ": fp32, or fp16 / bf16 on "
+                                << "GPU_HIP_IVF_FLAT";
+            return Status::invalid_args;
+        }
+        if (rt != KNHIP_ROWTYPE_FP32 && devs.size() > 1) {
+            if (!c.row_type.has_value()) {
+                rt = KNHIP_ROWTYPE_FP32;  // (the node type's default, not the caller's wish: a sharded index keeps fp32 rows)
+            } else {
+                LOG_KNOWHERE_ERROR_ << TypeName() << ": row_type " << c.row_type.value()
+                                    << " is not supported on an index sharded with gpu_ids";
+                return Status::invalid_args;
+            }
+        }
+        row_type_ = rt;
+        return Status::success;
+    }
+
     void
     DropShards() {
         group_.reset();
@@ -1406,6 +1444,9 @@ class HipIndexNode : public IndexNode {
             int rc = knhip_index_create(&desc, &sh_[r].idx.p);
             if constexpr (Kind == KNHIP_IVF_SQ8) {
                 if (rc == KNHIP_OK && sq_bits_ != 8) rc = knhip_index_set_sq_type(sh_[r].idx.p, (int32_t)sq_bits_);
+            }
+            if constexpr (Kind == KNHIP_IVF_FLAT) {
+                if (rc == KNHIP_OK && row_type_ != KNHIP_ROWTYPE_FP32) rc = knhip_index_set_row_type(sh_[r].idx.p, row_type_);
             }
             if (rc) {
                 DropShards();
@@ -1621,6 +1662,7 @@ class HipIndexNode : public IndexNode {
     uint64_t wire_nprobe_ = 1;  // the nprobe field of the serialized IVF header (Serialize)
     int64_t nbits_ = 8;  // IVF_PQ: code width (1 .. 8)
     int64_t sq_bits_ = 8;  // IVF_SQ8: code width of sq_type (SQ8 / SQ6 / SQ4)
+    int32_t row_type_ = DefaultRowType;  // IVF_FLAT: KNHIP_ROWTYPE_* the device keeps the rows in (config key row_type)
     std::vector<Shard> sh_;        // one entry: the whole index on one device; several: list- (FLAT: row-) sharded
     GroupHandle group_;            // several shards: the exchange + merge host (include/knhip_shards.h)
     std::vector<int32_t> owner_;   // several shards, IVF kinds: list -> shard
@@ -1665,17 +1707,25 @@ KNOWHERE_REGISTER_GLOBAL_WITH_THREAD_POOL(GPU_HIP_IVF_SQ8, HipIvfSqIndexNode, fp
                 thread_size));                                                                                             \
         },                                                                                                                 \
         data_type, typeCheck<data_type>(features), features)
-#define KNHIP_MOCK_REGISTER_TYPES(name, index_node)                                                                         \
-    KNHIP_MOCK_REGISTER_WITH_THREAD_POOL(name, index_node, fp16, knowhere::feature::GPU | knowhere::feature::FP16,         \
+#define KNHIP_MOCK_REGISTER_TYPES(name, node_fp16, node_bf16, node_int8)                                                    \
+    KNHIP_MOCK_REGISTER_WITH_THREAD_POOL(name, node_fp16, fp16, knowhere::feature::GPU | knowhere::feature::FP16,          \
                                          HipSearchPoolSize());                                                             \
-    KNHIP_MOCK_REGISTER_WITH_THREAD_POOL(name, index_node, bf16, knowhere::feature::GPU | knowhere::feature::BF16,         \
+    KNHIP_MOCK_REGISTER_WITH_THREAD_POOL(name, node_bf16, bf16, knowhere::feature::GPU | knowhere::feature::BF16,          \
                                          HipSearchPoolSize());                                                             \
-    KNHIP_MOCK_REGISTER_WITH_THREAD_POOL(name, index_node, int8, knowhere::feature::GPU | knowhere::feature::INT8,         \
+    KNHIP_MOCK_REGISTER_WITH_THREAD_POOL(name, node_int8, int8, knowhere::feature::GPU | knowhere::feature::INT8,          \
                                          HipSearchPoolSize());
-KNHIP_MOCK_REGISTER_TYPES(GPU_HIP_BRUTE_FORCE, HipBruteForceIndexNode)
-KNHIP_MOCK_REGISTER_TYPES(GPU_HIP_IVF_FLAT, HipIvfFlatIndexNode)
-KNHIP_MOCK_REGISTER_TYPES(GPU_HIP_IVF_PQ, HipIvfPqIndexNode)
-KNHIP_MOCK_REGISTER_TYPES(GPU_HIP_IVF_SQ8, HipIvfSqIndexNode)
+// GPU_HIP_IVF_FLAT keeps Float16Vector / BFloat16Vector data narrow on the device: the wrapper widens the dataset (exact),
+// the node's default row_type narrows it back (exact, nothing refused), and the kernels widen in registers.  The int8
+// registration stays on fp32 rows.  (This block is compiled against the reference's headers by
+// tests/test_node_contract.py; it is not built, and so not run, in the stand-alone shim build.)
+template <typename DataType>
+using HipIvfFlatFp16RowsIndexNode = HipIndexNode<DataType, KNHIP_IVF_FLAT, KNHIP_ROWTYPE_FP16>;
+template <typename DataType>
+using HipIvfFlatBf16RowsIndexNode = HipIndexNode<DataType, KNHIP_IVF_FLAT, KNHIP_ROWTYPE_BF16>;
+KNHIP_MOCK_REGISTER_TYPES(GPU_HIP_BRUTE_FORCE, HipBruteForceIndexNode, HipBruteForceIndexNode, HipBruteForceIndexNode)
+KNHIP_MOCK_REGISTER_TYPES(GPU_HIP_IVF_FLAT, HipIvfFlatFp16RowsIndexNode, HipIvfFlatBf16RowsIndexNode, HipIvfFlatIndexNode)
+KNHIP_MOCK_REGISTER_TYPES(GPU_HIP_IVF_PQ, HipIvfPqIndexNode, HipIvfPqIndexNode, HipIvfPqIndexNode)
+KNHIP_MOCK_REGISTER_TYPES(GPU_HIP_IVF_SQ8, HipIvfSqIndexNode, HipIvfSqIndexNode, HipIvfSqIndexNode)
 #endif
 
 }  // namespace knowhere

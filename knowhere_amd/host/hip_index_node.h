@@ -65,9 +65,14 @@ HipCheckMetric(const BaseConfig& cfg, PARAM_TYPE param_type, std::string* err_ms
 //            The reference's config system has no list type (include/knowhere/config.h:37-58), hence a string.  A
 //            device may be named twice ("0,0"): the shards then share it and exchange by device copies (tests on a
 //            one-GPU box).
+//   row_type "fp32" (default), "fp16" or "bf16", any letter case: the element type GPU_HIP_IVF_FLAT KEEPS its list rows in on
+//            the device (knhip_index_set_row_type).  Datasets, GetVectorByIds and the serialized blob stay fp32; rows that
+//            hold a value the type cannot represent exactly are refused (invalid_args), never rounded.  Every other index
+//            type refuses a value other than fp32, and so does an index sharded with gpu_ids.
 #define KNHIP_DEVICE_CONFIG_MEMBERS \
     CFG_INT gpu_id;                 \
-    CFG_STRING gpu_ids;
+    CFG_STRING gpu_ids;             \
+    CFG_STRING row_type;
 #define KNHIP_DEVICE_CONFIG_FIELDS()                                                                        \
     KNOWHERE_CONFIG_DECLARE_FIELD(gpu_id)                                                                   \
         .description("device ordinal of the index (unset: round-robin / most free memory)")                \
@@ -78,6 +83,12 @@ HipCheckMetric(const BaseConfig& cfg, PARAM_TYPE param_type, std::string* err_ms
         .for_deserialize_from_file();                                                                       \
     KNOWHERE_CONFIG_DECLARE_FIELD(gpu_ids)                                                                  \
         .description("devices the index is sharded over: comma separated ordinals or \"all\"")             \
+        .allow_empty_without_default()                                                                      \
+        .for_train()                                                                                        \
+        .for_deserialize()                                                                                  \
+        .for_deserialize_from_file();                                                                       \
+    KNOWHERE_CONFIG_DECLARE_FIELD(row_type)                                                                 \
+        .description("GPU_HIP_IVF_FLAT: element type of the rows on the device: fp32, fp16 or bf16")        \
         .allow_empty_without_default()                                                                      \
         .for_train()                                                                                        \
         .for_deserialize()                                                                                  \
@@ -109,6 +120,31 @@ HipParseGpuIds(const std::string& s, int ndev) {
     return out;
 }
 
+// "fp32" / "fp16" / "bf16" in any letter case -> KNHIP_ROWTYPE_* (0, 1, 2); -1 for any other name
+inline int32_t
+HipParseRowType(const std::string& s) {
+    std::string t;
+    for (char c : s) t.push_back((char)std::tolower((unsigned char)c));
+    return t == "fp32" ? 0 : t == "fp16" ? 1 : t == "bf16" ? 2 : -1;
+}
+
+// the row_type key, in every config: a known name, and a narrow type on GPU_HIP_IVF_FLAT only
+template <typename Cfg>
+inline Status
+HipCheckRowType(const Cfg& cfg, bool ivf_flat, std::string* err_msg) {
+    if (!cfg.row_type.has_value()) return Status::success;
+    const int32_t rt = HipParseRowType(cfg.row_type.value());
+    if (rt < 0) {
+        if (err_msg) *err_msg = "row_type \"" + cfg.row_type.value() + "\" is not one of fp32, fp16, bf16";
+        return Status::invalid_args;
+    }
+    if (rt != 0 && !ivf_flat) {
+        if (err_msg) *err_msg = "row_type " + cfg.row_type.value() + " is supported by GPU_HIP_IVF_FLAT only";
+        return Status::invalid_args;
+    }
+    return Status::success;
+}
+
 struct HipBruteForceConfig : public FlatConfig {
     KNHIP_DEVICE_CONFIG_MEMBERS
     KNOWHERE_DECLARE_CONFIG(HipBruteForceConfig) {
@@ -121,6 +157,7 @@ struct HipBruteForceConfig : public FlatConfig {
     }
     Status
     CheckAndAdjust(PARAM_TYPE param_type, std::string* err_msg) override {
+        RETURN_IF_ERROR(HipCheckRowType(*this, false, err_msg));
         return HipCheckMetric(*this, param_type, err_msg);
     }
 };
@@ -137,6 +174,7 @@ struct HipIvfFlatConfig : public IvfFlatConfig {
     }
     Status
     CheckAndAdjust(PARAM_TYPE param_type, std::string* err_msg) override {
+        RETURN_IF_ERROR(HipCheckRowType(*this, true, err_msg));
         return HipCheckMetric(*this, param_type, err_msg);
     }
 };
@@ -158,6 +196,7 @@ struct HipIvfPqConfig : public IvfPqConfig {
     }
     Status
     CheckAndAdjust(PARAM_TYPE param_type, std::string* err_msg) override {
+        RETURN_IF_ERROR(HipCheckRowType(*this, false, err_msg));
         RETURN_IF_ERROR(HipCheckMetric(*this, param_type, err_msg));
         if (param_type == PARAM_TYPE::TRAIN && m.has_value() && m.value() != 0) {
             const int mv = m.value();
@@ -192,6 +231,7 @@ struct HipIvfSqConfig : public IvfSqConfig {
     }
     Status
     CheckAndAdjust(PARAM_TYPE param_type, std::string* err_msg) override {
+        RETURN_IF_ERROR(HipCheckRowType(*this, false, err_msg));
         RETURN_IF_ERROR(HipCheckMetric(*this, param_type, err_msg));
         if (param_type == PARAM_TYPE::TRAIN && sq_type.has_value()) {
             std::string t = sq_type.value();

@@ -12,6 +12,7 @@ from ._lib import KnhipError, check  # noqa: F401
 
 BRUTE_FORCE, IVF_FLAT, IVF_PQ, IVF_SQ8 = _lib.BRUTE_FORCE, _lib.IVF_FLAT, _lib.IVF_PQ, _lib.IVF_SQ8
 L2, IP = _lib.L2, _lib.IP
+ROWTYPE_FP32, ROWTYPE_FP16, ROWTYPE_BF16 = _lib.ROWTYPE_FP32, _lib.ROWTYPE_FP16, _lib.ROWTYPE_BF16
 
 KIND_NAMES = {"GPU_HIP_BRUTE_FORCE": BRUTE_FORCE, "GPU_HIP_IVF_FLAT": IVF_FLAT, "GPU_HIP_IVF_PQ": IVF_PQ,
               "GPU_HIP_IVF_SQ8": IVF_SQ8}
@@ -40,14 +41,18 @@ def _bitset_nbits(bitset, nbits):
 
 class GpuIndex:
     def __init__(self, kind, metric, dim, nlist=0, pq_m=0, pq_nbits=8, device=0,
-                 precomputed_table_max_bytes=0, sq_type=8):
+                 precomputed_table_max_bytes=0, sq_type=8, row_type=0):
         """sq_type: IVF_SQ8 only, the code width of the list codes in bits -- 8 (default), 6 or 4, the reference's
-        sq_type SQ8 / SQ6 / SQ4; list codes are the reference's bytes, _lib.sq_code_size(dim, sq_type) per row"""
+        sq_type SQ8 / SQ6 / SQ4; list codes are the reference's bytes, _lib.sq_code_size(dim, sq_type) per row.
+        row_type: IVF_FLAT only, ROWTYPE_FP16 / ROWTYPE_BF16 keep the rows narrow on the device; everything that crosses the
+        boundary stays fp32, and rows holding a value the type cannot represent exactly are refused (KnhipError)"""
         self.L = _lib.load()
         self.kind, self.metric, self.dim, self.nlist, self.pq_m = kind, metric, dim, nlist, pq_m
         self.pq_nbits = pq_nbits
         self.device = device
         self.sq_type = int(sq_type)
+        if row_type not in (ROWTYPE_FP32, ROWTYPE_FP16, ROWTYPE_BF16) or (row_type != ROWTYPE_FP32 and kind != IVF_FLAT):
+            raise ValueError("row_type: ROWTYPE_FP32, ROWTYPE_FP16 or ROWTYPE_BF16, and other than fp32 on an IVF_FLAT index only")
         if self.sq_type != 8 and (kind != IVF_SQ8 or self.sq_type not in (6, 4)):
             raise ValueError("sq_type: 8, 6 or 4, and other than 8 on an IVF_SQ8 index only")
         d = _lib.Desc(kind, metric, dim, device, nlist, pq_m, pq_nbits, precomputed_table_max_bytes)
@@ -56,6 +61,13 @@ class GpuIndex:
         self.h = h
         if self.sq_type != 8:
             check(self.L.knhip_index_set_sq_type(self.h, self.sq_type))
+        if row_type != ROWTYPE_FP32:
+            check(self.L.knhip_index_set_row_type(self.h, int(row_type)))
+
+    @property
+    def row_type(self):
+        """ROWTYPE_* of the rows as the device keeps them (0 for every kind but IVF_FLAT)"""
+        return int(self.L.knhip_index_get_row_type(self.h))
 
     @property
     def code_size(self):
@@ -118,12 +130,12 @@ class GpuIndex:
         check(self.L.knhip_index_add_vectors(self.h, x.shape[0], _np_ptr(x), None, id_offset))
 
     @classmethod
-    def from_data(cls, ix, device=0, precomputed_table_max_bytes=0):
+    def from_data(cls, ix, device=0, precomputed_table_max_bytes=0, row_type=0):
         """ix: any object with the fields of oracle.binding.IndexData (duck typed; the product does
         not import the oracle)."""
         kind = {0: BRUTE_FORCE, 1: IVF_FLAT, 2: IVF_PQ, 3: IVF_SQ8}[ix.kind]
         g = cls(kind, ix.metric, ix.d, ix.nlist, ix.M, ix.nbits, device, precomputed_table_max_bytes,
-                sq_type=getattr(ix, "sq_type", 8))
+                sq_type=getattr(ix, "sq_type", 8), row_type=row_type)
         if kind == BRUTE_FORCE:
             g.add_vectors(ix.base)
             return g

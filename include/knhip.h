@@ -32,6 +32,10 @@
  *                                        IVFIteratorWorkspace.cpp:35-204, include/knowhere/index/index_node.h:1099-1247),
  *                                        BruteForce::AnnIterator + PrecomputedDistanceIterator
  *                                        (src/common/comp/brute_force.cc:1524-1760, index_node.h:1254-1390)
+ *   knhip_index_calc_dist*               IvfIndexNode::CalcDistByStorageIds (src/index/ivf/ivf.cc:1178-1227) over
+ *                                        IndexIVFFlat::calc_dist_by_ids (thirdparty/faiss/faiss/cppcontrib/knowhere/
+ *                                        IndexIVFFlat.cpp:665-763): the rerank primitive of the embedding-list strategies
+ *                                        (RerankByCalcDistByStorageIds, src/index/emb_list/emb_list_strategy.cc:45-117)
  *
  * Numeric contract ("exact" mode, the default): every distance is computed with the
  * reference's scalar operation order, one IEEE rounding per operation (no FMA contraction),
@@ -74,6 +78,7 @@ extern "C" {
  * Additive since 9 (new functions only, no structure touched, the version stays 9): the AnnIterator, knhip_iter_*.
  * Additive since 9: KNHIP_MAX_K, knhip_select_ordered_device (search and refine with 1024 < k <= 16384).
  * Additive since 9: knhip_index_set_row_type / knhip_index_get_row_type (IVF_FLAT rows kept as fp16 / bf16 in HBM).
+ * Additive since 9: knhip_index_calc_dist / knhip_index_calc_dist_device (CalcDistByIDs: exact distances to given ids).
  * Callers compare knhip_abi_version() with the header they were built against. */
 #define KNHIP_ABI_VERSION 9
 /* Largest k of a search and largest k_base of a refine (additive since 9: the large-k path, knhip_select_ordered_device). */
@@ -428,6 +433,23 @@ int knhip_index_get_vectors(const knhip_index* idx, int64_t n, const int64_t* id
  * range of a sharded FLAT): found[i] = 1 and out row i written where id i is stored here, found[i] = 0 and the row left
  * untouched otherwise; never an error for an absent id. */
 int knhip_index_find_vectors(const knhip_index* idx, int64_t n, const int64_t* ids, float* out, uint8_t* found);
+/* CalcDistByIDs (IndexNode::CalcDistByStorageIds / CalcDistByIDs, include/knowhere/index/index_node.h:168-204):
+ * out_dist[q * n_labels + j] = the distance a Search() of this index reports between query q and the stored vector whose
+ * id is labels[j] (IVF_FLAT: the id given at Add, found through the direct map; BRUTE_FORCE: row = id - id_offset) -- the same
+ * 32 bits: the scans' operation order, typed rows widened in registers, stored-norm COSINE applied as the scans apply it.
+ * No bitset (the reference's IVF implementation ignores the one it is handed).  Labels come in any order and may repeat;
+ * their number is not tied to KNHIP_MAX_K.  n_labels == 0 or nq == 0: KNHIP_OK, nothing touched.  IVF_PQ / IVF_SQ8:
+ * KNHIP_ERR_NOT_IMPLEMENTED (the reference: "only support IndexIVFFlat and IndexIVFFlatCC").
+ * Host form (host pointers), strict as knhip_index_get_vectors: an id that is not stored is KNHIP_ERR_INVALID_ARGS,
+ * knhip_last_error names the first such label and its position, out_dist is left unwritten.
+ * Device form (everything in HBM), tolerant: the columns of an absent id receive the all-ones bit pattern -- what
+ * knhip_refine_distances_device writes for "not held here", so knhip_refine_combine_device combines the shards' partial
+ * matrices unchanged -- and *d_nabsent (if not NULL; a device int64) receives the number of absent labels.  Enqueued on
+ * `stream`, not synchronised.  The first call after an Add on an IVF_FLAT index builds the direct map (it synchronises). */
+int knhip_index_calc_dist(const knhip_index* idx, const float* queries, int64_t nq, int64_t n_labels,
+                          const int64_t* labels, float* out_dist);
+int knhip_index_calc_dist_device(const knhip_index* idx, const float* d_queries, int64_t nq, int64_t n_labels,
+                                 const int64_t* d_labels, float* d_out_dist, int64_t* d_nabsent, void* stream);
 /* Same with every buffer already in HBM; enqueued on `stream` (hipStream_t, NULL = default
  * stream) and NOT synchronised at the end.  One exception inside: an IVF_PQ m = 32 batch that takes the matrix-core
  * prefilter (pq_filter.hip) waits once on `stream` in the middle of the batch the FIRST time a (k, nprobe) pair is seen

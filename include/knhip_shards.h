@@ -21,6 +21,7 @@
 #ifndef KNHIP_SHARDS_H
 #define KNHIP_SHARDS_H
 #include "knhip.h"
+#include <string.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -54,6 +55,36 @@ int knhip_shard_group_set_raw_rows(knhip_shard_group* g, int32_t rank, const knh
 int knhip_shard_group_search_refine(knhip_shard_group* g, const float* queries, int64_t nq, int32_t k, int32_t k_base,
                                     int32_t nprobe, const uint8_t* bitset, int64_t bitset_nbits, int64_t* out_ids,
                                     float* out_dist, float* stage_ms);
+/* CalcDistByIDs of the whole (sharded) index (knhip_index_calc_dist, include/knhip.h): host queries [nq][dim] and labels
+ * [n_labels] in, host distances [nq][n_labels] out.  Every rank runs knhip_index_calc_dist_device over the whole label list
+ * on the part it holds, the partial matrices are combined on the host, and the result is bit-identical to one index.  Strict as
+ * the host form: a label that NO rank holds is KNHIP_ERR_INVALID_ARGS (checked once, over all ranks; the message names the
+ * first such label and its position) and out_dist is left unwritten.  Needs no refine store and no collective. */
+int knhip_shard_group_calc_dist(knhip_shard_group* g, const float* queries, int64_t nq, int64_t n_labels,
+                                const int64_t* labels, float* out_dist);
+/* host equivalent of knhip_refine_combine_device for the partial matrices of knhip_index_calc_dist_device: out[e] = the first
+ * parts[r][e] that is not the all-ones pattern ("not held here"), the all-ones pattern when every rank wrote it */
+static inline void knhip_calc_dist_combine_host(int32_t nshards, int64_t n, const float* const* parts, float* out) {
+    for (int64_t e = 0; e < n; e++) {
+        uint32_t v = 0xffffffffu;
+        for (int32_t r = 0; r < nshards && v == 0xffffffffu; r++) {
+            memcpy(&v, &parts[r][e], sizeof(v));
+        }
+        memcpy(&out[e], &v, sizeof(v));
+    }
+}
+/* position of the first label whose column of a combined matrix holds the all-ones pattern (one row suffices: absence is a
+ * property of the column), -1 when every label was held */
+static inline int64_t knhip_calc_dist_first_absent_host(const float* row, int64_t n_labels) {
+    for (int64_t j = 0; j < n_labels; j++) {
+        uint32_t v;
+        memcpy(&v, &row[j], sizeof(v));
+        if (v == 0xffffffffu) {
+            return j;
+        }
+    }
+    return -1;
+}
 int32_t knhip_shard_group_size(const knhip_shard_group* g);
 /* message of the last failed knhip_shard_group_* call on this thread (the per-rank text: "rank r: ...") */
 const char* knhip_shard_group_last_error(void);

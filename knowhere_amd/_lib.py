@@ -63,7 +63,7 @@ SYMBOLS = [
     "knhip_fvec_L1_ny", "knhip_fvec_Linf_ny", "knhip_fvec_norms_L2sqr_ref", "knhip_fvec_L2sqr_ny_transposed",
     "knhip_fvec_L2sqr_ny_nearest", "knhip_fvec_L2sqr_ny_nearest_y_transposed", "knhip_fvec_madd_and_argmin",
     "knhip_fvec_batch_4", "knhip_typed_vec_ny", "knhip_typed_vec_batch_4", "knhip_ivec_ny",
-    "knhip_select_ordered_device",
+    "knhip_select_ordered_device", "knhip_index_calc_dist", "knhip_index_calc_dist_device",
     "knhip_iter_create", "knhip_iter_next", "knhip_iter_next_all", "knhip_iter_has_next", "knhip_iter_stats", "knhip_iter_destroy",
 ]
 
@@ -197,6 +197,8 @@ def load():
     L.knhip_search_refine.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, i64, vp, vp]
     L.knhip_index_get_vectors.argtypes = [vp, i64, vp, vp]
     L.knhip_index_find_vectors.argtypes = [vp, i64, vp, vp, vp]
+    L.knhip_index_calc_dist.argtypes = [vp, vp, i64, i64, vp, vp]
+    L.knhip_index_calc_dist_device.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp]
     L.knhip_index_assign.argtypes = [vp, i64, vp, vp]
     L.knhip_device_memory.argtypes = [i32, vp, vp]
     L.knhip_rows_create.argtypes = [i32, i32, i32, C.POINTER(vp)]

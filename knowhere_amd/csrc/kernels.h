@@ -706,6 +706,37 @@ hipError_t launch_rows_encode4u(const float* x, int64_t n, int d, const float* t
 hipError_t launch_rows_key_hist(const float* x, int64_t n, uint32_t mask, uint32_t prefix_lo, uint32_t prefix_hi, int shift,
                                 unsigned long long* hist, hipStream_t s);
 
+// CalcDistByIDs (refine.hip, calc_dist_kernel): out[q * out_stride + j] = the scan's distance between query q and the stored
+// row whose id is labels[j]; the all-ones pattern where the id is not stored here
+constexpr int CD_ROWS = 64;  // labels per tile: one lane per row
+constexpr int CD_QT = 32;    // queries per tile: eight per wave
+constexpr int CD_DIMS = 128; // dimensions per pass over the tile (48 KB of LDS with fp32 rows)
+struct CalcDistArgs {
+    const void* rows;             // interleaved 64-row blocks of 16-byte chunks (FlatScanArgs), or, aos = 1, row-major fp32 rows
+    int32_t aos;                  // 1: rows [ntotal][d] fp32 with d % 4 == 0 (a BRUTE_FORCE index's own copy)
+    const int64_t* idmap_ids;     // IVF_FLAT: the sorted direct map (build.hip launch_idmap_build) ...
+    const int64_t* idmap_col;     // ... and the column of each id's row; both nullptr: row = id - id_offset
+    int64_t ntotal;
+    int64_t id_offset;
+    int32_t d;
+    int32_t nchunk;               // row_nchunk(d, row type)
+    const float* queries;         // [nq][d]
+    int64_t nq;
+    const int64_t* labels;        // [nlabels]
+    int64_t nlabels;
+    int64_t label_base;           // position of labels[0] in the caller's list (first_absent is a position in that list)
+    float* out;
+    int64_t out_stride;           // floats between two queries' rows of `out`
+    const float* row_scale;       // COSINE with stored norms, one float per stored row position (FlatScanArgs)
+    int32_t cos_mode;
+    int32_t count_absent;         // 1: absent labels are counted (by the first query tile) into the two words below
+    unsigned long long* nabsent;      // += number of labels not stored here (nullptr: not wanted)
+    unsigned long long* first_absent; // min= position of such a label (nullptr: not wanted)
+};
+// a call is cut into launches of at most round_labels x round_queries pairs
+hipError_t launch_calc_dist(const CalcDistArgs& a, bool is_l2, int row_type, hipStream_t s,
+                            int64_t round_labels = (int64_t)1 << 22, int64_t round_queries = (int64_t)1 << 19);
+
 // ---- build.hip: Train / Add on the device ----
 // direct map of an IVF-Flat index (GetVectorByIds): ids sorted with the columns of their rows in the interleaved store
 size_t idmap_sort_tmp_bytes(int64_t n);

@@ -1372,6 +1372,107 @@ int knhip_index_find_vectors(const knhip_index* idx, int64_t n, const int64_t* i
     return KNHIP_OK;
 }
 
+// ---- CalcDistByIDs (IvfIndexNode::CalcDistByStorageIds, src/index/ivf/ivf.cc:1178-1227): the distances Search() would report
+// between every query and the stored rows of the given ids, one fused gather + contraction (refine.hip, calc_dist_kernel) ----
+static int calc_dist_check(const knhip_index* idx, const char* who, const void* q, int64_t nq, int64_t nl, const void* labels,
+                           const void* out, bool* nothing) {
+    if (int rc = check_index(idx)) return rc;
+    const int kind = idx->desc.kind;
+    if (kind != KNHIP_BRUTE_FORCE && kind != KNHIP_IVF_FLAT) {
+        return fail(KNHIP_ERR_NOT_IMPLEMENTED, std::string(who) + ": only BRUTE_FORCE and IVF_FLAT keep the rows (the reference: "
+                                                                  "only support IndexIVFFlat and IndexIVFFlatCC)");
+    }
+    if (nq < 0 || nl < 0) {
+        return fail(KNHIP_ERR_INVALID_ARGS, std::string(who) + ": negative count");
+    }
+    *nothing = nq == 0 || nl == 0;
+    if (!*nothing && (!q || !labels || !out)) {
+        return fail(KNHIP_ERR_INVALID_ARGS, std::string(who) + ": null query / label / output pointer");
+    }
+    return KNHIP_OK;
+}
+
+// enqueues on s; absent[0] += labels not stored here, absent[1] min= the position of one (either may be null)
+static int calc_dist_enqueue(const knhip_index* idx, const float* d_q, int64_t nq, int64_t nl, const int64_t* d_labels,
+                             float* d_out, unsigned long long* nabsent, unsigned long long* first_absent, hipStream_t s) {
+    CalcDistArgs a{};
+    if (idx->desc.kind == KNHIP_IVF_FLAT) {
+        if (int rc = ensure_idmap(idx)) return rc;
+        a.rows = idx->rows.p;
+        a.idmap_ids = idx->idmap_ids.as<int64_t>();
+        a.idmap_col = idx->idmap_col.as<int64_t>();
+        a.ntotal = a.idmap_ids ? idx->ntotal : 0;
+    } else {
+        // the row-major copy where its rows are whole 16-byte chunks (one run of 4 d bytes per row), else the interleaved blocks
+        a.aos = (idx->d & 3) == 0 && idx->codes_aos.p != nullptr;
+        a.rows = a.aos ? idx->codes_aos.p : idx->rows.p;
+        a.ntotal = a.rows ? idx->ntotal : 0;
+        a.id_offset = idx->id_offset;
+    }
+    const int rt = idx->desc.kind == KNHIP_IVF_FLAT ? idx->row_type : KN_ROW_FP32;
+    a.d = idx->d;
+    a.nchunk = row_nchunk(idx->d, rt);
+    a.queries = d_q;
+    a.nq = nq;
+    a.labels = d_labels;
+    a.nlabels = nl;
+    a.out = d_out;
+    a.out_stride = nl;
+    a.row_scale = idx->row_scale.as<float>();
+    a.cos_mode = idx->is_l2 ? 0 : idx->cos_mode;
+    a.count_absent = (nabsent || first_absent) ? 1 : 0;
+    a.nabsent = nabsent;
+    a.first_absent = first_absent;
+    HIP_TRY(launch_calc_dist(a, idx->is_l2, rt, s));
+    return KNHIP_OK;
+}
+
+int knhip_index_calc_dist_device(const knhip_index* idx, const float* d_queries, int64_t nq, int64_t n_labels,
+                                 const int64_t* d_labels, float* d_out_dist, int64_t* d_nabsent, void* stream) {
+    bool nothing = false;
+    if (int rc = calc_dist_check(idx, "calc_dist_device", d_queries, nq, n_labels, d_labels, d_out_dist, &nothing)) return rc;
+    if (nothing) {
+        return KNHIP_OK;
+    }
+    DeviceGuard g(idx->desc.device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (d_nabsent) {
+        HIP_TRY(hipMemsetAsync(d_nabsent, 0, sizeof(int64_t), s));
+    }
+    return calc_dist_enqueue(idx, d_queries, nq, n_labels, d_labels, d_out_dist, reinterpret_cast<unsigned long long*>(d_nabsent),
+                             nullptr, s);
+}
+
+int knhip_index_calc_dist(const knhip_index* idx, const float* queries, int64_t nq, int64_t n_labels, const int64_t* labels,
+                          float* out_dist) {
+    bool nothing = false;
+    if (int rc = calc_dist_check(idx, "calc_dist", queries, nq, n_labels, labels, out_dist, &nothing)) return rc;
+    if (nothing) {
+        return KNHIP_OK;
+    }
+    DeviceGuard g(idx->desc.device);
+    DevBuf dq, dl, dout, dabs;
+    if (int rc = upload(dq, queries, (size_t)nq * idx->d * sizeof(float))) return rc;
+    if (int rc = upload(dl, labels, (size_t)n_labels * sizeof(int64_t))) return rc;
+    HIP_TRY(dout.alloc((size_t)nq * (size_t)n_labels * sizeof(float)));
+    const unsigned long long init[2] = {0ull, ~0ull};
+    if (int rc = upload(dabs, init, sizeof(init))) return rc;
+    if (int rc = calc_dist_enqueue(idx, dq.as<float>(), nq, n_labels, dl.as<int64_t>(), dout.as<float>(),
+                                   dabs.as<unsigned long long>(), dabs.as<unsigned long long>() + 1, nullptr)) {
+        return rc;
+    }
+    unsigned long long absent[2] = {0ull, 0ull};
+    HIP_TRY(hipMemcpy(absent, dabs.p, sizeof(absent), hipMemcpyDeviceToHost)); // (the one read-back: waits for the kernels)
+    if (absent[0] != 0ull) {
+        const int64_t pos = (int64_t)absent[1];
+        return fail(KNHIP_ERR_INVALID_ARGS, "calc_dist: label " + std::to_string(labels[pos]) + " at position " +
+                                                    std::to_string(pos) + " is not in the index (" +
+                                                    std::to_string(absent[0]) + " absent)");
+    }
+    HIP_TRY(hipMemcpy(out_dist, dout.p, (size_t)nq * (size_t)n_labels * sizeof(float), hipMemcpyDeviceToHost));
+    return KNHIP_OK;
+}
+
 // ---- sharded refine: distances where the rows are, ONE selection over all of them --------------------------------------------
 int knhip_refine_distances_device(int32_t metric, int32_t dim, const float* d_base, int64_t nbase, int64_t id_base,
                                   const float* d_queries, int64_t nq, const int64_t* d_cand_ids, int32_t k_base,

@@ -581,4 +581,206 @@ hipError_t launch_rows_encode_i8(const float* x, int64_t n_elems, uint8_t* out, 
     return hipGetLastError();
 }
 
+// ---- CalcDistByIDs: the nq x L matrix of exact distances between the queries and the stored rows of L given ids --------------
+// Replaces IndexIVFFlat::calc_dist_by_ids (reference thirdparty/faiss/faiss/cppcontrib/knowhere/IndexIVFFlat.cpp:665-763: per
+// query, per label, the direct map's (list, offset), then fvec_L2sqr / fvec_inner_product over the row, divided by the stored
+// norm when the lists keep norms) behind IvfIndexNode::CalcDistByStorageIds (src/index/ivf/ivf.cc:1178-1227).
+// One workgroup = a tile of CD_ROWS labels x CD_QT queries.  The labels' rows are located once per tile (IVF_FLAT: a binary
+// search of the sorted direct map; BRUTE_FORCE: id - id_offset), their 16-byte chunks gathered from the resident layout into
+// LDS as [chunk][row] (pitch CD_ROWS + 1 pieces: a lane group of the gather writes consecutive chunks of one row, 4 banks
+// apart; the compute reads consecutive rows of one chunk), and every wave runs 8 of the tile's queries over them with lane =
+// row: the steps of flat_scan.hip in dimension order, the row value from LDS, the query value a broadcast read.  A gathered
+// row is fetched once per query tile.  Rows wider than CD_DIMS dimensions take several passes over the same accumulators.
+// Zero-padded dimensions (d % 4, typed rows d % 8) take the steps the scans take on them.
+constexpr int CD_PITCH = CD_ROWS + 1;
+
+template <bool IS_L2, int RT>
+__global__ __launch_bounds__(256) void calc_dist_kernel(const CalcDistArgs a) {
+    constexpr int CDIMS = RT == KN_ROW_FP32 ? 4 : 8;    // dimensions per 16-byte chunk
+    constexpr int NCP = CD_DIMS / CDIMS;                // chunks per pass
+    constexpr int NPT = CD_ROWS * NCP / 256;            // pieces per thread and pass
+    constexpr int QW = CD_QT / 4;                       // queries per wave
+    __shared__ uint4 s_rows[NCP * CD_PITCH];
+    __shared__ float4 s_q4[CD_QT * CD_DIMS / 4]; // (16-byte aligned by its type: the waves read it in 16-byte pieces)
+    float* s_q = reinterpret_cast<float*>(s_q4);
+    __shared__ int64_t s_col[CD_ROWS];
+    const int lane = lane_id();
+    const int wave = threadIdx.x / KN_WAVE;
+    const int64_t j0 = (int64_t)blockIdx.x * CD_ROWS;   // first label of the tile
+    const int64_t q0 = (int64_t)blockIdx.y * CD_QT;     // first query
+    // ---- locate the rows: column of the interleaved store (BRUTE_FORCE: the row number), -1 = not stored here
+    if (threadIdx.x < CD_ROWS) {
+        const int64_t j = j0 + threadIdx.x;
+        int64_t col = -1;
+        if (j < a.nlabels) {
+            const int64_t id = a.labels[j];
+            if (a.idmap_ids == nullptr) {
+                const uint64_t r = (uint64_t)id - (uint64_t)a.id_offset;
+                col = r < (uint64_t)a.ntotal ? (int64_t)r : -1;
+            } else {
+                int64_t lo = 0, hi = a.ntotal;
+                while (lo < hi) { // first entry >= id
+                    const int64_t mid = (lo + hi) >> 1;
+                    if (a.idmap_ids[mid] < id) {
+                        lo = mid + 1;
+                    } else {
+                        hi = mid;
+                    }
+                }
+                if (lo < a.ntotal && a.idmap_ids[lo] == id) {
+                    col = a.idmap_col[lo];
+                }
+            }
+            if (col < 0 && a.count_absent && blockIdx.y == 0) {
+                if (a.nabsent != nullptr) {
+                    atomicAdd(a.nabsent, 1ull);
+                }
+                if (a.first_absent != nullptr) {
+                    atomicMin(a.first_absent, (unsigned long long)(a.label_base + j));
+                }
+            }
+        }
+        s_col[threadIdx.x] = col;
+    }
+    __syncthreads();
+    const int nqw = (int)max((int64_t)0, min((int64_t)QW, a.nq - q0 - wave * QW)); // live queries of this wave
+    float acc[QW];
+#pragma unroll
+    for (int jq = 0; jq < QW; jq++) {
+        acc[jq] = 0.f;
+    }
+    const uint4* src = reinterpret_cast<const uint4*>(a.rows);
+    for (int c0 = 0; c0 < a.nchunk; c0 += NCP) {
+        const int ncp = min(NCP, a.nchunk - c0);
+        if (c0 > 0) {
+            __syncthreads(); // (the pass before is read)
+        }
+        // ---- the tile's queries, dimensions [c0 * CDIMS, + ncp * CDIMS), zero beyond d and beyond nq
+        const int nd = ncp * CDIMS;
+        for (int t = threadIdx.x; t < CD_QT * nd; t += 256) {
+            const int qi = t / nd, i = t % nd;
+            const int dim = c0 * CDIMS + i;
+            s_q[qi * CD_DIMS + i] = (q0 + qi < a.nq && dim < a.d) ? a.queries[(q0 + qi) * a.d + dim] : 0.f;
+        }
+        // ---- the rows' chunks c0 .. c0 + ncp: consecutive threads take consecutive chunks of one row, all loads first
+        uint4 v[NPT];
+#pragma unroll
+        for (int u = 0; u < NPT; u++) {
+            const int p = threadIdx.x + u * 256;
+            const int r = p / ncp, c = p % ncp;
+            v[u] = make_uint4(0u, 0u, 0u, 0u);
+            if (r < CD_ROWS) {
+                const int64_t col = s_col[r];
+                if (col >= 0) {
+                    v[u] = a.aos ? src[col * a.nchunk + c0 + c]
+                                 : src[(col >> 6) * (int64_t)a.nchunk * 64 + (int64_t)(c0 + c) * 64 + (col & 63)];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NPT; u++) {
+            const int p = threadIdx.x + u * 256;
+            const int r = p / ncp, c = p % ncp;
+            if (r < CD_ROWS) {
+                s_rows[c * CD_PITCH + r] = v[u];
+            }
+        }
+        __syncthreads();
+        if (nqw > 0) {
+            const float* wq = s_q + wave * QW * CD_DIMS;
+#pragma unroll 2
+            for (int c = 0; c < ncp; c++) {
+                const uint4 w = s_rows[c * CD_PITCH + lane];
+                if constexpr (RT != KN_ROW_FP32) {
+#pragma unroll
+                    for (int jq = 0; jq < QW; jq++) {
+                        acc[jq] = row_chunk8_steps<IS_L2, RT>(acc[jq], w, wq + jq * CD_DIMS + c * 8);
+                    }
+                } else {
+                    const float4 y = make_float4(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z),
+                                                 __uint_as_float(w.w));
+#pragma unroll
+                    for (int jq = 0; jq < QW; jq++) {
+                        const float4 q = *reinterpret_cast<const float4*>(wq + jq * CD_DIMS + c * 4);
+                        if (IS_L2) {
+                            acc[jq] = l2_step(acc[jq], q.x, y.x);
+                            acc[jq] = l2_step(acc[jq], q.y, y.y);
+                            acc[jq] = l2_step(acc[jq], q.z, y.z);
+                            acc[jq] = l2_step(acc[jq], q.w, y.w);
+                        } else {
+                            acc[jq] = ip_step(acc[jq], q.x, y.x);
+                            acc[jq] = ip_step(acc[jq], q.y, y.y);
+                            acc[jq] = ip_step(acc[jq], q.z, y.z);
+                            acc[jq] = ip_step(acc[jq], q.w, y.w);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    // ---- lane = row: one coalesced 256-byte store per query
+    const int64_t j = j0 + lane;
+    if (j >= a.nlabels) {
+        return;
+    }
+    const int64_t col = s_col[lane];
+    float sc = 1.0f;
+    if (!IS_L2 && a.cos_mode != 0 && col >= 0) {
+        sc = a.row_scale[col];
+    }
+#pragma unroll
+    for (int jq = 0; jq < QW; jq++) {
+        if (jq < nqw) {
+            float dis = acc[jq];
+            if (!IS_L2 && a.cos_mode != 0) { // COSINE with stored norms (FlatScanArgs)
+                dis = cosine_finish(dis, sc, a.cos_mode);
+            }
+            a.out[(q0 + wave * QW + jq) * a.out_stride + j] = col >= 0 ? dis : __uint_as_float(REFINE_NOT_HERE);
+        }
+    }
+}
+
+hipError_t launch_calc_dist(const CalcDistArgs& args, bool is_l2, int row_type, hipStream_t s, int64_t round_labels,
+                            int64_t round_queries) {
+    if (args.nq <= 0 || args.nlabels <= 0) {
+        return hipSuccess;
+    }
+    if (row_type < KN_ROW_FP32 || row_type > KN_ROW_BF16 || (args.aos && row_type != KN_ROW_FP32) || round_labels <= 0 ||
+        round_queries <= 0 || (!is_l2 && args.cos_mode != 0 && args.row_scale == nullptr)) {
+        return hipErrorInvalidValue;
+    }
+    // rounds: a launch takes at most round_labels x round_queries pairs (whole tiles; the grid's y extent stays under 65536)
+    round_labels = (std::min<int64_t>(round_labels, (int64_t)1 << 24) + CD_ROWS - 1) / CD_ROWS * CD_ROWS;
+    round_queries = (std::min<int64_t>(round_queries, (int64_t)1 << 20) + CD_QT - 1) / CD_QT * CD_QT;
+    for (int64_t l0 = 0; l0 < args.nlabels; l0 += round_labels) {
+        for (int64_t q0 = 0; q0 < args.nq; q0 += round_queries) {
+            CalcDistArgs a = args;
+            a.labels = args.labels + l0;
+            a.nlabels = std::min(round_labels, args.nlabels - l0);
+            a.label_base = args.label_base + l0;
+            a.queries = args.queries + q0 * args.d;
+            a.nq = std::min(round_queries, args.nq - q0);
+            a.out = args.out + q0 * args.out_stride + l0;
+            a.count_absent = args.count_absent && q0 == 0; // (an absent label is counted once, by its first query tile)
+            const dim3 grid((unsigned)((a.nlabels + CD_ROWS - 1) / CD_ROWS), (unsigned)((a.nq + CD_QT - 1) / CD_QT));
+#define KN_CD_LAUNCH(RT_)                                                                                  \
+    if (is_l2) {                                                                                           \
+        hipLaunchKernelGGL((calc_dist_kernel<true, RT_>), grid, dim3(256), 0, s, a);                       \
+    } else {                                                                                               \
+        hipLaunchKernelGGL((calc_dist_kernel<false, RT_>), grid, dim3(256), 0, s, a);                      \
+    }
+            switch (row_type) {
+                case KN_ROW_FP16: KN_CD_LAUNCH(KN_ROW_FP16); break;
+                case KN_ROW_BF16: KN_CD_LAUNCH(KN_ROW_BF16); break;
+                default: KN_CD_LAUNCH(KN_ROW_FP32); break;
+            }
+#undef KN_CD_LAUNCH
+            if (hipError_t e = hipGetLastError(); e != hipSuccess) {
+                return e;
+            }
+        }
+    }
+    return hipSuccess;
+}
+
 } // namespace knhip

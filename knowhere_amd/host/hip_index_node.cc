@@ -836,6 +836,51 @@ class HipIndexNode : public IndexNode {
         return GenResultDataSet(n, dim_, (const void*)out.release());
     }
 
+    // IvfIndexNode::CalcDistByStorageIds (ivf.cc:1178-1227; include/knowhere/index/index_node.h:168-179): the nq x labels_len
+    // matrix of the distances this index's own Search reports for the rows of the given storage ids -- one fused gather +
+    // contraction on the device (knhip_index_calc_dist) where the reference loops query by query, row by row.  is_cosine: the
+    // queries are copied and normalised as Search does (ivf.cc:1207-1210).  The bitset is ignored, as the reference's IVF
+    // implementation ignores the one it is handed.  Result: rows = nq, dim = labels_len, distances only.  GPU_HIP_BRUTE_FORCE
+    // is served too (the reference's FlatIndexNode leaves the default); IVF_PQ / IVF_SQ8: not_implemented with the reference's
+    // message.  An id that is not stored: invalid_args (the reference throws inside faiss: faiss_inner_error).  A node sharded
+    // with gpu_ids: every shard computes the columns of the rows it holds, combined on the host, absent ids checked once.
+    expected<DataSetPtr>
+    CalcDistByStorageIds(const DataSetPtr dataset, const BitsetView& /*bitset*/, const int64_t* labels, const size_t labels_len,
+                         const bool is_cosine, milvus::OpContext* op_context) const override {
+        using R = expected<DataSetPtr>;
+        if constexpr (Kind == KNHIP_IVF_PQ || Kind == KNHIP_IVF_SQ8) {
+            // only support IndexIVFFlat and IndexIVFFlatCC (ivf.cc:1224-1226)
+            return R::Err(Status::not_implemented, "CalcDistByStorageIds not implemented for current index type");
+        }
+        if (!dataset || (dataset->GetRows() > 0 && !dataset->GetTensor())) return R::Err(Status::invalid_args, "null dataset");
+        if (labels_len > 0 && !labels) return R::Err(Status::invalid_args, "null labels");
+        if (!Built() || Count() == 0) return R::Err(Status::empty_index, "index not built");
+        if (dataset->GetDim() != dim_) return R::Err(Status::invalid_args, "dim mismatch");
+        checkCancellation(op_context);
+        const int64_t nq = dataset->GetRows();
+        const int64_t nl = (int64_t)labels_len;
+        const float* q = (const float*)dataset->GetTensor();
+        std::vector<float> qn;
+        if (is_cosine && nq > 0) {  // CopyAndNormalizeVecs (ivf.cc:1207-1210)
+            qn.assign(q, q + nq * dim_);
+            NormalizeRows(qn.data(), nq, dim_);
+            q = qn.data();
+        }
+        auto dis = std::make_unique<float[]>((size_t)std::max<int64_t>(nq * nl, 1));
+        if (nq > 0 && nl > 0) {
+            std::shared_lock<std::shared_mutex> lk(rw_);
+            if (sh_.size() == 1) {
+                const int rc = knhip_index_calc_dist(sh_[0].idx.p, q, nq, nl, labels, dis.get());
+                if (rc) return R::Err(ToStatus(rc), knhip_last_error());
+            } else {
+                const int rc = knhip_shard_group_calc_dist(group_.p, q, nq, nl, labels, dis.get());
+                if (rc) return R::Err(ToStatus(rc), knhip_shard_group_last_error());
+            }
+        }
+        // (ids are not used in this context: ivf.cc:1220-1221)
+        return GenResultDataSet(nq, nl, static_cast<const int64_t*>(nullptr), static_cast<const float*>(dis.release()));
+    }
+
     static bool
     StaticHasRawData(const knowhere::BaseConfig& config, const IndexVersion& /*version*/) {
         // cosine stores normalised vectors (IvfIndexNode::StaticHasRawData semantics, ivf.cc:142-160)

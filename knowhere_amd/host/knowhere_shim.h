@@ -715,6 +715,21 @@ class IdMap {
             if (ids[i] >= 0 && (size_t)ids[i] < in_to_out_.size()) ids[i] = in_to_out_[ids[i]];
         }
     }
+    // public ids -> backend storage ids, in order; public ids without a stored row are left out (id_map.h CompactOutToIn:
+    // "missing nullable public ids are ignored").  Identity unless a map is installed.
+    void CompactOutToIn(const int64_t* out_ids, size_t count, std::vector<int64_t>& compact_ids) const {
+        compact_ids.clear();
+        if (in_to_out_.empty()) {
+            compact_ids.assign(out_ids, out_ids + count);
+            return;
+        }
+        std::map<int64_t, int64_t> out_to_in;
+        for (size_t i = 0; i < in_to_out_.size(); i++) out_to_in.emplace(in_to_out_[i], (int64_t)i);
+        for (size_t i = 0; i < count; i++) {
+            auto it = out_to_in.find(out_ids[i]);
+            if (it != out_to_in.end()) compact_ids.push_back(it->second);
+        }
+    }
 
  private:
     std::vector<int64_t> in_to_out_;
@@ -861,6 +876,27 @@ class IndexNode : public Object {
                 milvus::OpContext* op_context = nullptr) const {
         return expected<DataSetPtr>::Err(Status::not_implemented, "RangeSearch not implemented");
     }
+    // exact distances for ids already in the base-vector storage domain (include/knowhere/index/index_node.h:168-179)
+    virtual expected<DataSetPtr>
+    CalcDistByStorageIds(const DataSetPtr dataset, const BitsetView& bitset, const int64_t* labels, const size_t labels_len,
+                         const bool is_cosine, milvus::OpContext* op_context = nullptr) const {
+        return expected<DataSetPtr>::Err(Status::not_implemented, "CalcDistByStorageIds not implemented");
+    }
+    // ... and for public ids: compacted to storage ids first (index_node.h:181-204)
+    virtual expected<DataSetPtr>
+    CalcDistByIDs(const DataSetPtr dataset, const BitsetView& bitset, const int64_t* labels, const size_t labels_len,
+                  const bool is_cosine, milvus::OpContext* op_context = nullptr) const {
+        if (dataset == nullptr) {
+            return expected<DataSetPtr>::Err(Status::invalid_args, "CalcDistByIDs dataset is null");
+        }
+        std::vector<int64_t> storage_ids;
+        GetIdMap().CompactOutToIn(labels, labels_len, storage_ids);
+        if (storage_ids.empty()) {
+            return GenResultDataSet(dataset->GetRows(), 0, static_cast<const int64_t*>(nullptr),
+                                    static_cast<const float*>(nullptr));
+        }
+        return CalcDistByStorageIds(dataset, bitset, storage_ids.data(), storage_ids.size(), is_cosine, op_context);
+    }
     // (include/knowhere/index/index_node.h:205-237: not thread safe; errors come back in the expected<>)
     class iterator {
      public:
@@ -967,6 +1003,13 @@ class IndexNodeThreadPoolWrapper : public IndexNode {
     }
     expected<DataSetPtr> GetVectorByIds(const DataSetPtr dataset, milvus::OpContext* op_context) const override {
         return index_node_->GetVectorByIds(dataset, op_context);
+    }
+    // (the wrapped node's, as index_node_data_mock_wrapper.cc:98-102 forwards it)
+    expected<DataSetPtr> CalcDistByStorageIds(const DataSetPtr dataset, const BitsetView& bitset, const int64_t* labels,
+                                              const size_t labels_len, const bool is_cosine,
+                                              milvus::OpContext* op_context) const override {
+        Slot s(this);
+        return index_node_->CalcDistByStorageIds(dataset, bitset, labels, labels_len, is_cosine, op_context);
     }
     bool HasRawData(const std::string& metric_type) const override { return index_node_->HasRawData(metric_type); }
     bool NeedBitsetExactCount() const override { return index_node_->NeedBitsetExactCount(); }
@@ -1123,6 +1166,18 @@ class Index {
     GetVectorByIds(const DataSetPtr dataset, milvus::OpContext* op_context = nullptr) const noexcept {
         try {
             return node_->GetVectorByIds(dataset, op_context);
+        } catch (const std::exception& e) {
+            return expected<DataSetPtr>::Err(Status::knowhere_inner_error, e.what());
+        }
+    }
+    // (src/index/index.cc:371-383: the bitset projected to the backend id domain, the public ids compacted by the node)
+    expected<DataSetPtr>
+    CalcDistByIDs(const DataSetPtr dataset, const BitsetView& bitset, const int64_t* labels, const size_t labels_len,
+                  const bool is_cosine, milvus::OpContext* op_context = nullptr) const noexcept {
+        try {
+            return node_->CalcDistByIDs(dataset, node_->PrepareBitset(bitset), labels, labels_len, is_cosine, op_context);
+        } catch (const OperationCancelled& e) {
+            return expected<DataSetPtr>::Err(Status::timeout, e.what());
         } catch (const std::exception& e) {
             return expected<DataSetPtr>::Err(Status::knowhere_inner_error, e.what());
         }

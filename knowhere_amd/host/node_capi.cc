@@ -205,6 +205,26 @@ int knhip_node_get_vectors(void* h, const int64_t* ids, int64_t n, int64_t dim, 
     return 0;
 }
 
+// Index::CalcDistByIDs: q [nq][dim], labels [n_labels] (public ids; identity unless an id map is installed); out receives
+// nq * n_labels floats.  Returns the Status (0 = success), the text through knhip_node_last_error.
+int knhip_node_calc_dist_by_ids(void* h, const float* q, int64_t nq, int64_t dim, const int64_t* labels, int64_t n_labels,
+                                int32_t is_cosine, float* out) {
+    auto ds = GenDataSet(nq, dim, q);
+    auto r = static_cast<Handle*>(h)->idx.CalcDistByIDs(ds, BitsetView(), labels, (size_t)n_labels, is_cosine != 0);
+    if (!r.has_value()) {
+        g_err = r.what();
+        return (int)r.error();
+    }
+    if (r.value()->GetRows() != nq || r.value()->GetDim() != n_labels || r.value()->GetIds() != nullptr) {
+        g_err = "CalcDistByIDs: result shape is not rows = nq, dim = labels_len, distances only";
+        return (int)knowhere::Status::knowhere_inner_error;
+    }
+    if (nq * n_labels > 0) {
+        std::memcpy(out, r.value()->GetDistance(), sizeof(float) * (size_t)(nq * n_labels));
+    }
+    return 0;
+}
+
 // where the index built / loaded last on the calling thread was placed (device ordinals in shard order): test hook
 int32_t knhip_node_last_placement(int32_t* out, int32_t cap) { return knhip_host_last_placement(out, cap); }
 

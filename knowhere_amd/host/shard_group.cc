@@ -718,6 +718,84 @@ int knhip_shard_group_search_refine(knhip_shard_group* g, const float* queries, 
     return search_impl(g, queries, nq, k, k_base, nprobe, bitset, bitset_nbits, out_ids, out_dist, stage_ms);
 }
 
+// CalcDistByIDs of the whole (sharded) index: every rank runs knhip_index_calc_dist_device over the WHOLE label list on the
+// part it holds (the columns of the labels it does not hold come back as the all-ones pattern), the partial matrices are
+// combined on the host (knhip_calc_dist_combine_host: a label is held by one rank, so the combined value is that rank's --
+// the bits of one index), and a label is absent when NO rank held it: checked once, over all ranks, on the first query's row.
+// Queries go in slices that bound the host staging to 64 MB per rank.  No collective: the ranks' streams only.
+int knhip_shard_group_calc_dist(knhip_shard_group* g, const float* queries, int64_t nq, int64_t n_labels, const int64_t* labels,
+                                float* out_dist) {
+    if (!g || nq < 0 || n_labels < 0) return fail(KNHIP_ERR_INVALID_ARGS, "shard_group_calc_dist: bad arguments");
+    knhip_desc desc{};
+    for (const Rank& r : g->ranks) {
+        if (!r.idx) return fail(KNHIP_ERR_INVALID_ARGS, "shard_group_calc_dist: a rank has no index");
+        if (int rc = knhip_index_get_desc(r.idx, &desc)) return fail(rc, knhip_last_error());
+    }
+    if (nq == 0 || n_labels == 0) return KNHIP_OK;
+    if (!queries || !labels || !out_dist) return fail(KNHIP_ERR_INVALID_ARGS, "shard_group_calc_dist: null query / label / output pointer");
+    std::lock_guard<std::mutex> call_lk(g->call_mu);
+    const int W = g->n;
+    const int64_t d = desc.dim;
+    const int64_t qstep = std::max<int64_t>(1, ((int64_t)1 << 24) / n_labels);
+    std::vector<std::vector<float>> parts((size_t)W);
+    std::vector<float> comb;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    int rc = KNHIP_OK;
+    std::string err;
+    auto run = [&]() {
+        for (int64_t q0 = 0; q0 < nq; q0 += qstep) {
+            const int64_t n = std::min(qstep, nq - q0);
+            const size_t ne = (size_t)n * (size_t)n_labels;
+            for (int r = 0; r < W; r++) {  // enqueue on every rank's stream ...
+                Rank& k = g->ranks[r];
+                parts[(size_t)r].resize(ne);
+                SG_HIP(hipSetDevice(k.dev));
+                SG_HIP(k.q.reserve((size_t)n * d * sizeof(float)));
+                SG_HIP(k.keys.reserve((size_t)n_labels * sizeof(int64_t)));
+                SG_HIP(k.rdist.reserve(ne * sizeof(float)));
+                SG_HIP(hipMemcpyAsync(k.q.p, queries + q0 * d, (size_t)n * d * sizeof(float), hipMemcpyHostToDevice, k.stream));
+                SG_HIP(hipMemcpyAsync(k.keys.p, labels, (size_t)n_labels * sizeof(int64_t), hipMemcpyHostToDevice, k.stream));
+                if (int c = knhip_index_calc_dist_device(k.idx, static_cast<const float*>(k.q.p), n, n_labels,
+                                                         static_cast<const int64_t*>(k.keys.p), static_cast<float*>(k.rdist.p),
+                                                         nullptr, k.stream)) {
+                    rc = c;
+                    err = std::string("rank ") + std::to_string(r) + ": " + knhip_last_error();
+                    return;
+                }
+                SG_HIP(hipMemcpyAsync(parts[(size_t)r].data(), k.rdist.p, ne * sizeof(float), hipMemcpyDeviceToHost, k.stream));
+            }
+            for (int r = 0; r < W; r++) {  // ... then wait for each
+                SG_HIP(hipSetDevice(g->ranks[r].dev));
+                SG_HIP(hipStreamSynchronize(g->ranks[r].stream));
+            }
+            comb.resize(ne);
+            std::vector<const float*> pp((size_t)W);
+            for (int r = 0; r < W; r++) pp[(size_t)r] = parts[(size_t)r].data();
+            knhip_calc_dist_combine_host(W, (int64_t)ne, pp.data(), comb.data());
+            if (q0 == 0) {
+                const int64_t absent = knhip_calc_dist_first_absent_host(comb.data(), n_labels);
+                if (absent >= 0) {
+                    rc = KNHIP_ERR_INVALID_ARGS;
+                    err = "calc_dist: label " + std::to_string(labels[absent]) + " at position " + std::to_string(absent) +
+                          " is not in the index";
+                    return;
+                }
+            }
+            std::memcpy(out_dist + q0 * n_labels, comb.data(), ne * sizeof(float));
+        }
+    };
+    run();
+    if (rc != KNHIP_OK) {  // (nothing of a failed call stays queued behind the caller's back)
+        for (Rank& k : g->ranks) {
+            (void)hipSetDevice(k.dev);
+            (void)hipStreamSynchronize(k.stream);
+        }
+    }
+    (void)hipSetDevice(prev);
+    return rc == KNHIP_OK ? KNHIP_OK : fail(rc, err);
+}
+
 const char* knhip_shard_group_last_error() { return g_err.c_str(); }
 
 }  // extern "C"

@@ -285,6 +285,16 @@ class GpuIndex:
         check(self.L.knhip_index_get_vectors(self.h, len(ids), _np_ptr(ids), _np_ptr(out)))
         return out
 
+    def calc_dist(self, xq, labels):
+        """CalcDistByIDs (knhip_index_calc_dist) -> [nq, L] float32: the distances a search of this index reports between
+        every query and the stored vectors of the given ids (any order, repeats allowed); an id that is not stored is an
+        error.  BRUTE_FORCE and IVF_FLAT."""
+        xq = np.ascontiguousarray(xq, np.float32).reshape(-1, self.dim)
+        labels = np.ascontiguousarray(labels, np.int64).reshape(-1)
+        out = np.empty((xq.shape[0], len(labels)), np.float32)
+        check(self.L.knhip_index_calc_dist(self.h, _np_ptr(xq), xq.shape[0], len(labels), _np_ptr(labels), _np_ptr(out)))
+        return out
+
     def last_range_ranks(self):
         """coarse ranks per query the last range_search scanned (rank waves: knhip_index_last_range_ranks)"""
         return int(self.L.knhip_index_last_range_ranks(self.h))
@@ -342,6 +352,18 @@ class GpuIndex:
         check(self.L.knhip_search_device(self.h, _t_ptr(xq_t), nq, k, nprobe, _t_ptr(bitset_t), nbits,
                                          _t_ptr(I), _t_ptr(D), C.c_void_p(s)))
         return D, I
+
+    def calc_dist_device(self, xq_t, labels_t, out=None, stream=None):
+        """knhip_index_calc_dist_device -> (D [nq, L] float32, nabsent [1] int64), device tensors, enqueued on the stream: the
+        columns of a label that is not stored here hold the all-ones bit pattern (refine_select_device's "not held here")"""
+        import torch
+        nq, nl = xq_t.shape[0], labels_t.shape[0]
+        D = torch.empty((nq, nl), dtype=torch.float32, device=xq_t.device) if out is None else out
+        nabsent = torch.zeros(1, dtype=torch.int64, device=xq_t.device)
+        s = torch.cuda.current_stream(xq_t.device).cuda_stream if stream is None else stream
+        check(self.L.knhip_index_calc_dist_device(self.h, _t_ptr(xq_t), nq, nl, _t_ptr(labels_t), _t_ptr(D), _t_ptr(nabsent),
+                                                  C.c_void_p(s)))
+        return D, nabsent
 
     def search_preassigned_device(self, xq_t, k, keys_t, cdis_t, bitset_t=None, nbits=0, stream=None):
         """search with a given coarse assignment (keys_t / cdis_t: [nq][nprobe] from coarse_search_device)"""

@@ -293,8 +293,11 @@ int bf_rows_batch(const knhip_index* idx, Workspace* ws, const Batch& b, hipStre
 }
 
 // BRUTE_FORCE on the matrix cores (ensure_bf_split): a chunk's (nq, k) result -> slot `slot` of [nq][nslots][k], rows -> ids
+// (the selection of the coarse stage keeps the k best rows whatever their distance; the reference's heap starts at the neutral
+// value and admits strictly better distances only: a row at an infinite L2 distance -- or at the neutral value itself -- is
+// no result.  Such entries sort last in their chunk, so neutralising them leaves the chunk's list padded as the reference's.)
 __global__ void bf_place_kernel(const int64_t* __restrict__ keys, const float* __restrict__ dis, int64_t nq, int k, int64_t add,
-                                float* __restrict__ pd, int64_t* __restrict__ pi, int nslots, int slot) {
+                                float* __restrict__ pd, int64_t* __restrict__ pi, int nslots, int slot, bool is_l2) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nq * k) {
         return;
@@ -302,8 +305,10 @@ __global__ void bf_place_kernel(const int64_t* __restrict__ keys, const float* _
     const int64_t q = t / k, j = t % k;
     const int64_t o = (q * nslots + slot) * k + j;
     const int64_t key = keys[t];
-    pd[o] = dis[t];
-    pi[o] = key >= 0 ? key + add : -1;
+    const float v = dis[t];
+    const bool admitted = key >= 0 && (is_l2 ? v < FLT_MAX : v > -FLT_MAX);
+    pd[o] = admitted ? v : (is_l2 ? FLT_MAX : -FLT_MAX);
+    pi[o] = admitted ? key + add : -1;
 }
 
 int bf_mfma_batch(const knhip_index* idx, Workspace* ws, const Batch& b, int64_t per, hipStream_t s) {
@@ -338,7 +343,7 @@ int bf_mfma_batch(const knhip_index* idx, Workspace* ws, const Batch& b, int64_t
                 }
                 hipLaunchKernelGGL(bf_place_kernel, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, s, ws->keys.as<int64_t>(),
                                    ws->cdis.as<float>(), n, k, r0 + idx->id_offset, ws->partial_d.as<float>() + q0 * nch * k,
-                                   ws->partial_i.as<int64_t>() + q0 * nch * k, (int)nch, (int)c);
+                                   ws->partial_i.as<int64_t>() + q0 * nch * k, (int)nch, (int)c, idx->is_l2);
                 HIP_TRY(hipGetLastError());
             }
         }

@@ -613,6 +613,14 @@ __device__ __forceinline__ void ms_codes_to_f16(const uint4 w, ms_f16x8& lo8, ms
 // One wave per query: y' = q vdiff / 255 scaled by sc = 2^ex (max |y'| sc in [2^9, 2^10)) and split into halves hi + lo
 // -> qh / ql [nq][ldq] (zero padded to the step multiple); qs[q] = {sc, A, W, sum |y'|, sum (hi + lo), finite?, 0, 0}.
 // The same arithmetic as the in-kernel prologue below.
+// The scale 2^ex brings max |y'| into [2^9, 2^10) -- unless ex met its clamp: above 2^70 the scaled values leave the half
+// range (inf, then NaN from the matrix cores), below 2^-51 they sink into half's subnormals and then to zero, and the split
+// hi + lo no longer carries y' to the 2^-22 the error bound counts on.  Such a pair has no prefilter: its query takes the
+// exact kernels (the "no bound" route), and its rows of the sample pass are dumped as the neutral value.
+__device__ __forceinline__ bool ms_sq_scale_fits(float mx, float sc) {
+    return mx == 0.f || (mx * sc >= 512.0f && mx * sc < 1024.0f); // (false for inf and NaN)
+}
+
 template <int BITS>
 __global__ __launch_bounds__(256) void ms_sq8_query_prep_kernel(const float* __restrict__ queries, int64_t nq, int d,
                                                                 int ldq, const float* __restrict__ trained,
@@ -641,12 +649,13 @@ __global__ __launch_bounds__(256) void ms_sq8_query_prep_kernel(const float* __r
         ex = max(-60, min(60, ex));
     }
     const float sc = ldexpf(1.0f, ex);
+    const bool fits = ms_sq_scale_fits(mx, sc);
     float sA = 0.f, sW = 0.f, sYp = 0.f, sHL = 0.f;
     for (int i = lane; i < ldq; i += KN_WAVE) {
         _Float16 h = (_Float16)0.f, l = (_Float16)0.f;
         if (i < d) {
             const float y = qv[i];
-            const float yp = y * vdiff[i] * MS_INV * sc;
+            const float yp = fits ? y * vdiff[i] * MS_INV * sc : 0.f;
             h = (_Float16)yp;
             l = (_Float16)(yp - (float)h);
             sA += y * (vmin[i] + 0.5f * vdiff[i] * MS_INV);
@@ -668,7 +677,7 @@ __global__ __launch_bounds__(256) void ms_sq8_query_prep_kernel(const float* __r
         o[2] = sW;
         o[3] = sYp;
         o[4] = sHL;
-        o[5] = (mx < INFINITY) ? 1.f : 0.f;
+        o[5] = fits ? 1.f : 0.f;
         o[6] = 0.f;
         o[7] = 0.f;
     }
@@ -758,6 +767,10 @@ __device__ __forceinline__ void mscan_sq8_unit(const MScanArgs a, const int64_t 
                 ex = max(-60, min(60, ex));
             }
             float sc = ldexpf(1.0f, ex);
+            const bool fits = prepared || ms_sq_scale_fits(mx, sc);
+            if (!fits) {
+                mx = INFINITY;
+            }
             float sA = 0.f, sW = 0.f, sYp = 0.f, sHL = 0.f, sR = 0.f;
             if (prepared) {
                 const float* o = a.qs + (int64_t)q * 8;
@@ -772,7 +785,7 @@ __device__ __forceinline__ void mscan_sq8_unit(const MScanArgs a, const int64_t 
                 _Float16 h = (_Float16)0.f, l = (_Float16)0.f;
                 if (i < d) {
                     const float y = IS_L2 ? (qv[i] - cen[i]) : qv[i];
-                    const float yp = y * vdiff[i] * MS_INV * sc;
+                    const float yp = fits ? y * vdiff[i] * MS_INV * sc : 0.f;
                     h = (_Float16)yp;
                     l = (_Float16)(yp - (float)h);
                     sA += y * (vmin[i] + 0.5f * vdiff[i] * MS_INV);
@@ -815,10 +828,16 @@ __device__ __forceinline__ void mscan_sq8_unit(const MScanArgs a, const int64_t 
             offv = off;
             u0 = IS_L2 ? (sR - 2.0f * sA + eps) : (dis0 + sA - eps);
             vv = IS_L2 ? -2.0f / sc : 1.0f / sc;
+            // (operands that do not fit their scale were zeroed above; an eps or a u0 that overflowed certifies nothing)
+            const bool usable = mx < INFINITY && eps < INFINITY && fabsf(u0) < INFINITY;
+            if (DUMP && !usable) { // the sample pass: this pair's rows give no bound (acc = 0: the neutral value as it stands)
+                u0 = worst_dist<IS_L2>();
+                vv = 0.f;
+            }
             if (!DUMP) {
                 float tau = a.gthr[q];
                 tau = tighter<IS_L2>(tau, ms_hist_bound<IS_L2>(a, q, a.k));
-                if (tau == worst_dist<IS_L2>() || !(mx < INFINITY)) {
+                if (tau == worst_dist<IS_L2>() || !usable || !(tau == tau)) {
                     // no bound (fewer than k unfiltered rows in the sample): every row would pass -> exact fallback
                     if (lane == 0) {
                         a.overflow[q] = 1;
@@ -1128,7 +1147,10 @@ __global__ void ms_tau_kernel(const float* __restrict__ sel_d, int64_t nq, int k
     if (q >= nq) {
         return;
     }
-    const float kth = sel_d[q * k + k - 1]; // the neutral value when the sample holds fewer than k unfiltered rows
+    float kth = sel_d[q * k + k - 1]; // the neutral value when the sample holds fewer than k unfiltered rows
+    if (!(kth == kth)) { // a NaN is no bound: the exact kernels behind the filter compare against gthr too
+        kth = worst_dist<IS_L2>();
+    }
     gthr[q] = kth;
     if (gmeta != nullptr) {
         uint32_t lo = 0, shift = KN_HIST_OFF;

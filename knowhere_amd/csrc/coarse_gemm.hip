@@ -24,6 +24,7 @@
 //      on the margin being "big enough".
 #include "common.h"
 #include "kernels.h"
+#include "knhip_env.h"
 
 namespace knhip {
 
@@ -435,7 +436,8 @@ __global__ __launch_bounds__(256, 2) void coarse_bf16_kernel(const unsigned char
 }
 
 // B_q = the ncand-th best of the query's G group minima (gmin [nq][G]): one wave per query, the row in registers,
-// bisection over the order-preserving integer keys with ballot counts.  G <= 4096.
+// bisection over the order-preserving integer keys with ballot counts.  G <= 4096.  (Launched under KNHIP_COARSE_BOUND=v1
+// only: coarse_bound_reg_kernel below returns the same bits with the registers the row needs.)
 template <bool IS_L2>
 __global__ __launch_bounds__(256) void coarse_bound_kernel(const float* __restrict__ gmin, int G, int64_t nq, int ncand,
                                                            float* __restrict__ bound) {
@@ -471,6 +473,76 @@ __global__ __launch_bounds__(256) void coarse_bound_kernel(const float* __restri
     }
     if (lane == 0) {
         bound[q] = cr_unkey_fwd<IS_L2>(lo);
+    }
+}
+
+// The same bound with as many key registers as the row needs (R = 8, 16, 32 or 64 registers of 64 keys, picked at launch:
+// the kernel above walks 64 predicated slots per step whatever G is, 8 of them hold data at G = 512) and the bisection
+// started from the row's own [smallest, largest] key: the keys of one row share their exponent, so the interval is a few
+// 2^20 wide, not 2^32.  The result is the unique ncand-th smallest key either way.
+template <bool IS_L2, int R>
+__global__ __launch_bounds__(256) void coarse_bound_reg_kernel(const float* __restrict__ gmin, int G, int64_t nq, int ncand,
+                                                               float* __restrict__ bound) {
+    const int lane = lane_id();
+    const int64_t q = (int64_t)blockIdx.x * (blockDim.x / KN_WAVE) + threadIdx.x / KN_WAVE;
+    if (q >= nq) {
+        return;
+    }
+    uint32_t key[R];
+    uint32_t kmin = 0xffffffffu, kmax = 0u;
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const int g = r * KN_WAVE + lane;
+        const bool have = g < G;
+        key[r] = have ? cr_key_fwd<IS_L2>(gmin[q * G + g]) : 0xffffffffu;
+        kmin = min(kmin, key[r]);
+        kmax = have ? max(kmax, key[r]) : kmax;
+    }
+#pragma unroll
+    for (int off = KN_WAVE / 2; off > 0; off >>= 1) {
+        kmin = min(kmin, (uint32_t)__shfl_xor((int)kmin, off, KN_WAVE));
+        kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, off, KN_WAVE));
+    }
+    // smallest key x with count(key <= x) >= ncand: count(key <= kmax) = G and count(key < kmin) = 0, so it lies in
+    // [kmin, kmax] when 1 <= ncand <= G; outside that the full interval gives 0 / 0xffffffff
+    uint32_t lo = kmin, hi = kmax;
+    if (ncand <= 0) {
+        lo = hi = 0u;
+    } else if (ncand > G) {
+        lo = hi = 0xffffffffu;
+    }
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        int cnt = 0;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            cnt += __popcll(__ballot(key[r] <= mid));
+        }
+        if (cnt >= ncand) {
+            hi = mid;
+        } else {
+            lo = mid + 1;
+        }
+    }
+    if (lane == 0) {
+        bound[q] = cr_unkey_fwd<IS_L2>(lo);
+    }
+}
+
+template <bool IS_L2>
+static void coarse_bound_launch(const float* gmin, int G, int64_t nq, int ncand, float* bound, hipStream_t s) {
+    const dim3 grid((unsigned)((nq + 3) / 4)), block(256);
+    const int nreg = (G + KN_WAVE - 1) / KN_WAVE;
+    if (knhip_host::env_kernels().coarse_bound_v1 || nreg > 64) {
+        hipLaunchKernelGGL((coarse_bound_kernel<IS_L2>), grid, block, 0, s, gmin, G, nq, ncand, bound);
+    } else if (nreg <= 8) {
+        hipLaunchKernelGGL((coarse_bound_reg_kernel<IS_L2, 8>), grid, block, 0, s, gmin, G, nq, ncand, bound);
+    } else if (nreg <= 16) {
+        hipLaunchKernelGGL((coarse_bound_reg_kernel<IS_L2, 16>), grid, block, 0, s, gmin, G, nq, ncand, bound);
+    } else if (nreg <= 32) {
+        hipLaunchKernelGGL((coarse_bound_reg_kernel<IS_L2, 32>), grid, block, 0, s, gmin, G, nq, ncand, bound);
+    } else {
+        hipLaunchKernelGGL((coarse_bound_reg_kernel<IS_L2, 64>), grid, block, 0, s, gmin, G, nq, ncand, bound);
     }
 }
 
@@ -730,7 +802,7 @@ hipError_t launch_coarse_bf16(const void* q_split, const float* qnorm, const voi
         if (!bound_given) {
             hipLaunchKernelGGL((coarse_bf16_kernel<true, 1>), dim3(grid), dim3(256), 0, s, Qs, qnorm, Cs, cnorm, nq, nlist, nslab, tq,
                                ntiles, gmin, G, nullptr, nullptr, nullptr, 0, g16);
-            hipLaunchKernelGGL((coarse_bound_kernel<true>), dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, gmin, G, nq, ncand, bound);
+            coarse_bound_launch<true>(gmin, G, nq, ncand, bound, s);
         }
         hipLaunchKernelGGL((coarse_bf16_kernel<true, 2>), dim3(grid), dim3(256), 0, s, Qs, qnorm, Cs, cnorm, nq, nlist, nslab, tq,
                            ntiles, nullptr, G, bound, cand_cnt, cand, cap, g16);
@@ -738,7 +810,7 @@ hipError_t launch_coarse_bf16(const void* q_split, const float* qnorm, const voi
         if (!bound_given) {
             hipLaunchKernelGGL((coarse_bf16_kernel<false, 1>), dim3(grid), dim3(256), 0, s, Qs, qnorm, Cs, cnorm, nq, nlist, nslab, tq,
                                ntiles, gmin, G, nullptr, nullptr, nullptr, 0, g16);
-            hipLaunchKernelGGL((coarse_bound_kernel<false>), dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, gmin, G, nq, ncand, bound);
+            coarse_bound_launch<false>(gmin, G, nq, ncand, bound, s);
         }
         hipLaunchKernelGGL((coarse_bf16_kernel<false, 2>), dim3(grid), dim3(256), 0, s, Qs, qnorm, Cs, cnorm, nq, nlist, nslab, tq,
                            ntiles, nullptr, G, bound, cand_cnt, cand, cap, g16);

@@ -3,7 +3,7 @@
 // they pick between kernels that return the same bits, size scratch, or switch experiments on.  The library never reads the
 // environment anywhere else.
 //
-// Two moments of reading, by what the tests and tools rely on:
+// Three moments of reading, by what the tests and tools rely on (the third: KERNEL switches, at a kernel's launch, below):
 //   * LAYOUT switches: read when an index lays out its lists / takes its rows / takes its coarse quantizer -- the index keeps
 //     what it read, a later change of the variable does not touch an existing index;
 //   * SEARCH switches: read by every search (tests flip them between two searches of one index: KNHIP_TIES,
@@ -89,6 +89,20 @@ inline long long env_add_slice_rows(int d) {
         return std::atoll(v);
     }
     return std::max<long long>(1, ((long long)1 << 30) / ((long long)d * 4));
+}
+
+// KERNEL switches: read by the launcher of a kernel that replaced another one returning the same bits, at every launch
+// (tests compare the two in one process).
+struct EnvKernels {
+    bool pqd_qprep_v1;     // KNHIP_PQD_QPREP=v1: pqd_query_prep_kernel, one query per workgroup
+    bool coarse_bound_v1;  // KNHIP_COARSE_BOUND=v1: coarse_bound_kernel with 64 key registers, bisecting [0, 2^32)
+};
+
+inline EnvKernels env_kernels() {
+    EnvKernels e{};
+    e.pqd_qprep_v1 = env_is(std::getenv("KNHIP_PQD_QPREP"), "v1");
+    e.coarse_bound_v1 = env_is(std::getenv("KNHIP_COARSE_BOUND"), "v1");
+    return e;
 }
 
 inline EnvSearch env_search() {

@@ -41,6 +41,7 @@
 // IVFPQScanner_impl.h:109-181) -- only WHICH rows reach the exact finish.
 #include "common.h"
 #include "kernels.h"
+#include "knhip_env.h"
 #include "ms_common.h"
 
 #include <algorithm>
@@ -236,6 +237,7 @@ hipError_t launch_pqd_index_prep(const float4* cb, const float* centroids, int64
 // ---- per batch: the queries' half rows and error records ---------------------------------------------------------------
 // one workgroup per query, thread = code c.  qh16[q][128] = half(sc_q q); qd[q] = {||q||_1, B_q, eps_base, 2 B_q}.
 // cst = the index constants above; pabs_max = max_v sum_m |term2| (L2 with the precomputed table; 0 for the inner product)
+// (Launched under KNHIP_PQD_QPREP=v1 only: pqd_query_prep_multi_kernel below writes the same bits.)
 template <bool IS_L2>
 __global__ __launch_bounds__(PD_KSUB) void pqd_query_prep_kernel(const float* __restrict__ queries, const float4* __restrict__ cb,
                                                                  const float* __restrict__ cst, float pabs_max,
@@ -301,10 +303,123 @@ __global__ __launch_bounds__(PD_KSUB) void pqd_query_prep_kernel(const float* __
     }
 }
 
+// The same records, PD_QP_Q queries per workgroup: a thread keeps its code's 32 codebook entries (as magnitudes) in
+// registers and applies them to every query of the workgroup, so the 128 KB codebook leaves the L2 once per PD_QP_Q queries
+// and not once per query (10^4 queries: 1.3 GB of L2 reads, 70 - 80 us on their own, for a few microseconds of arithmetic).
+// Bit-identical to the kernel above: a lane's 32 sums are formed by the same expression, the maximum over the codes is
+// order-free (folded across the wave by a transposing butterfly -- 32 exchanges per query and wave for all 32
+// sub-quantizers instead of 6 each --, across the waves on the bit patterns as the atomic of the kernel above does), and
+// one thread per query sums B_q over m = 0 .. 31 and ||q||_1 over i = 0 .. 127 in that order.
+constexpr int PD_QP_Q = 8;
+
+// v[0 .. 2 H) of every lane -> v[0 .. H): the lanes l and l ^ H share the work, each keeps the maxima of one half
+template <int H>
+__device__ __forceinline__ void pd_fold_max(float (&v)[PD_M], int lane) {
+    const bool up = (lane & H) != 0;
+#pragma unroll
+    for (int i = 0; i < H; i++) {
+        const float keep = up ? v[i + H] : v[i];
+        const float send = up ? v[i] : v[i + H];
+        v[i] = fmaxf(keep, __shfl_xor(send, H, KN_WAVE));
+    }
+}
+
+template <bool IS_L2>
+__global__ __launch_bounds__(PD_KSUB) void pqd_query_prep_multi_kernel(const float* __restrict__ queries, const float4* __restrict__ cb,
+                                                                       const float* __restrict__ cst, float pabs_max, int64_t nq,
+                                                                       _Float16* __restrict__ qh16, float* __restrict__ qd) {
+    constexpr int NW = PD_KSUB / KN_WAVE;
+    __align__(16) __shared__ float s_q[PD_QP_Q][PD_D];
+    __shared__ uint32_t s_max[PD_QP_Q][NW][PD_M];
+    const int c = threadIdx.x;
+    const int lane = lane_id();
+    const int wave = c / KN_WAVE;
+    const int64_t q0 = (int64_t)blockIdx.x * PD_QP_Q;
+    const int nqb = nq - q0 < PD_QP_Q ? (int)(nq - q0) : PD_QP_Q; // (the last workgroup's may be fewer)
+    float4 e[PD_M];
+#pragma unroll
+    for (int m = 0; m < PD_M; m++) {
+        e[m] = cb[m * PD_KSUB + c];
+    }
+    for (int i = c; i < nqb * PD_D; i += PD_KSUB) {
+        s_q[i / PD_D][i % PD_D] = queries[q0 * PD_D + i];
+    }
+    __syncthreads();
+    const float inv_y = cst[1], ysum = cst[3], sc_q = cst[4], inv_q = cst[5], inv_sc = cst[7];
+    for (int i = c; i < nqb * PD_D; i += PD_KSUB) {
+        qh16[q0 * PD_D + i] = (_Float16)(s_q[i / PD_D][i % PD_D] * sc_q); // (out of the half range: inf here, eps = inf below)
+    }
+    for (int j = 0; j < nqb; j++) {
+        float v[PD_M];
+#pragma unroll
+        for (int m = 0; m < PD_M; m++) {
+            const float4 x = *reinterpret_cast<const float4*>(&s_q[j][4 * m]);
+            v[m] = fabsf(x.x) * fabsf(e[m].x) + fabsf(x.y) * fabsf(e[m].y) + fabsf(x.z) * fabsf(e[m].z) + fabsf(x.w) * fabsf(e[m].w);
+        }
+        pd_fold_max<16>(v, lane);
+        pd_fold_max<8>(v, lane);
+        pd_fold_max<4>(v, lane);
+        pd_fold_max<2>(v, lane);
+        pd_fold_max<1>(v, lane);
+        const float w = fmaxf(v[0], __shfl_xor(v[0], 32, KN_WAVE)); // sub-quantizer lane & 31, over the wave's 64 codes
+        if (lane < PD_M) {
+            s_max[j][wave][lane] = __float_as_uint(w);
+        }
+    }
+    __syncthreads();
+    if (c < nqb) {
+        const int64_t q = q0 + c;
+        float B = 0.f, q1 = 0.f;
+        bool fits = true;
+        for (int m = 0; m < PD_M; m++) {
+            uint32_t b = 0u; // (the bit patterns, as the atomic maximum of the kernel above: a NaN query is caught below)
+            for (int w = 0; w < NW; w++) {
+                b = max(b, s_max[c][w][m]);
+            }
+            B += __uint_as_float(b);
+        }
+        for (int i = 0; i < PD_D; i++) {
+            q1 += fabsf(s_q[c][i]);
+            fits = fits && fabsf(s_q[c][i]) * sc_q < 65504.0f; // (false for NaN / inf too)
+        }
+        B *= 1.0001f; // (its own fp32 summation)
+        q1 *= 1.0001f;
+        float eps = INFINITY;
+        if (fits && B < INFINITY) {
+            const float F = IS_L2 ? 2.0f : 1.0f;
+            const float e_prod = (2.0f * PD_UH + PD_UH * PD_UH) * B;
+            const float e_sub = PD_A * (1.0f + PD_UH) * (ysum * inv_q + q1 * inv_y) + 128.0f * PD_A * PD_A * inv_sc;
+            const float e_acc = 136.0f * PD_U * ((1.0f + 3.0f * PD_UH) * B + 0.5f * pabs_max);
+            eps = (F * (e_prod + e_sub + e_acc) + 128.0f * PD_U * (pabs_max + F * B)) * 1.001f;
+#if defined(PD_EXP) && (PD_EXP & 32)
+            eps *= 16.0f; // (experiment build, as above)
+#endif
+#if defined(PD_EXP) && (PD_EXP & 64)
+            eps *= 0.25f; // (experiment build, as above: NOT a bound any more)
+#endif
+        }
+        qd[q * 4 + 0] = q1;
+        qd[q * 4 + 1] = B;
+        qd[q * 4 + 2] = eps;
+        qd[q * 4 + 3] = 2.0f * B;
+    }
+}
+
 hipError_t launch_pqd_query_prep(const float* queries, const float4* cb, const float* cst, int64_t nq, bool is_l2,
                                  float pabs_max, void* qh16, float* qd, hipStream_t s) {
     if (nq <= 0) {
         return hipSuccess;
+    }
+    if (!knhip_host::env_kernels().pqd_qprep_v1) {
+        const unsigned grid = (unsigned)((nq + PD_QP_Q - 1) / PD_QP_Q);
+        if (is_l2) {
+            hipLaunchKernelGGL(pqd_query_prep_multi_kernel<true>, dim3(grid), dim3(PD_KSUB), 0, s, queries, cb, cst, pabs_max, nq,
+                               static_cast<_Float16*>(qh16), qd);
+        } else {
+            hipLaunchKernelGGL(pqd_query_prep_multi_kernel<false>, dim3(grid), dim3(PD_KSUB), 0, s, queries, cb, cst, 0.f, nq,
+                               static_cast<_Float16*>(qh16), qd);
+        }
+        return hipGetLastError();
     }
     if (is_l2) {
         hipLaunchKernelGGL(pqd_query_prep_kernel<true>, dim3((unsigned)nq), dim3(PD_KSUB), 0, s, queries, cb, cst, pabs_max,

@@ -79,6 +79,7 @@ extern "C" {
  * Additive since 9: KNHIP_MAX_K, knhip_select_ordered_device (search and refine with 1024 < k <= 16384).
  * Additive since 9: knhip_index_set_row_type / knhip_index_get_row_type (IVF_FLAT rows kept as fp16 / bf16 in HBM).
  * Additive since 9: knhip_index_calc_dist / knhip_index_calc_dist_device (CalcDistByIDs: exact distances to given ids).
+ * Additive since 9: knhip_index_prepare / knhip_index_prepare_bytes / knhip_index_prepared (the lazily built layouts, up front).
  * Callers compare knhip_abi_version() with the header they were built against. */
 #define KNHIP_ABI_VERSION 9
 /* Largest k of a search and largest k_base of a refine (additive since 9: the large-k path, knhip_select_ordered_device). */
@@ -272,6 +273,39 @@ int knhip_index_get_desc(const knhip_index* idx, knhip_desc* out);  /* the descr
 int64_t knhip_index_count(const knhip_index* idx);         /* stored vectors */
 int64_t knhip_index_device_bytes(const knhip_index* idx);  /* HBM held by the index */
 int knhip_index_uses_precomputed_table(const knhip_index* idx);
+
+/* ---- prepare: the layouts a search would build on first use, built up front (additive to ABI 9) --------------------------
+ * Some layouts of an index are built by the first call that needs them (under the index's mutex, each with its own device
+ * synchronisation): the rows' norms of the IVF_FLAT / IVF_SQ8 prefilter, the IVF_PQ prefilter's term-2 sums, decode-form
+ * codebook and start values, half / int8 token streams, the skewed IVF_PQ layout of k > 128, the split-bf16 operand copy +
+ * norms of BRUTE_FORCE on the matrix cores, the IVF_FLAT direct map.  knhip_index_prepare builds, for the index AS IT STANDS
+ * NOW, every one of them that any of the given shapes would build: it asks the search's own plan (the routing function the
+ * search calls, with the shape split into the batches, and raised to the k + 1 of the boundary rule, exactly as
+ * knhip_search does), and where the IVF_PQ prefilter's guard picks the form only after its sample pass it builds what every
+ * form the guard may pick needs (decode form and half tables; the int8 form only under KNHIP_PQF_FORM=int8), plus the
+ * skewed layout when the exact fallback of that shape reads it.  nshapes == 0: the union over every shape of a search and
+ * every use.  uses == 0 counts as KNHIP_PREP_SEARCH.  Range search, the AnnIterator and the large-k path (k > 1024) read
+ * only what every index holds: their bits are accepted and build nothing.  KNHIP_PREP_GET_VECTORS / _CALC_DIST: the IVF_FLAT
+ * direct map.  Cumulative and idempotent (a second call with the same shapes launches nothing); all kernels on one stream,
+ * one synchronisation at the end; the index's mutex is held as the lazy builders hold it, so concurrent searches stay
+ * correct.  An allocation failure returns KNHIP_ERR_OUT_OF_MEMORY, knhip_last_error names the layout and its size; layouts
+ * finished before it stay, the failed one is released, and the index remains searchable (the lazy builders still work).
+ * knhip_index_prepare_bytes is the dry run: *extra_bytes = what knhip_index_device_bytes will grow by -- exact, a closed
+ * form of the list lengths and the shapes; no HIP call, nothing allocated.  (knhip_index_device_bytes counts the rows' norms
+ * of the prefilter since this entry point exists.)  Per-search workspace scratch (work tables, candidate lists, the decode
+ * form's spill area, ...) belongs to the search's stream, not to the index: neither function counts or allocates it.
+ * Every Add invalidates as before; knhip_index_prepared: 1 after a successful prepare, 0 again after the next Add. */
+enum { KNHIP_PREP_SEARCH = 1, KNHIP_PREP_RANGE = 2, KNHIP_PREP_ITER = 4, KNHIP_PREP_GET_VECTORS = 8, KNHIP_PREP_CALC_DIST = 16 };
+typedef struct knhip_prepare_shape {
+    int64_t nq;
+    int32_t k;
+    int32_t nprobe;      /* clamped to nlist; ignored by BRUTE_FORCE */
+    int32_t with_bitset; /* 0 / 1: the search passes a bitset */
+    int32_t uses;        /* bit set of KNHIP_PREP_* */
+} knhip_prepare_shape;
+int knhip_index_prepare(knhip_index* idx, const knhip_prepare_shape* shapes, int32_t nshapes);
+int knhip_index_prepare_bytes(const knhip_index* idx, const knhip_prepare_shape* shapes, int32_t nshapes, int64_t* extra_bytes);
+int knhip_index_prepared(const knhip_index* idx);
 
 /* Range search: every vector strictly inside the radius (L2: dist < radius, IP: dist > radius) among the
  * lists visited in coarse order, with the reference's early stop after `max_empty_result_buckets`

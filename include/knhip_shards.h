@@ -85,6 +85,14 @@ static inline int64_t knhip_calc_dist_first_absent_host(const float* row, int64_
     }
     return -1;
 }
+/* knhip_index_prepare / knhip_index_prepare_bytes (include/knhip.h) of the whole (sharded) index: the shapes go to every
+ * rank's index as they are (every rank scans the whole batch over the lists it owns), each on a worker thread of its own.
+ * prepare: the first failing rank's status ("rank r: ..." in knhip_shard_group_last_error); the other ranks still finish.
+ * prepare_bytes: extra_bytes [n_devices], entry r = what rank r's index would grow by on device_ids[r] (ranks sharing a
+ * device: the device's figure is the sum of theirs). */
+int knhip_shards_prepare(knhip_shard_group* g, const knhip_prepare_shape* shapes, int32_t nshapes);
+int knhip_shards_prepare_bytes(const knhip_shard_group* g, const knhip_prepare_shape* shapes, int32_t nshapes,
+                               int64_t* extra_bytes);
 int32_t knhip_shard_group_size(const knhip_shard_group* g);
 /* message of the last failed knhip_shard_group_* call on this thread (the per-rank text: "rank r: ...") */
 const char* knhip_shard_group_last_error(void);

@@ -65,7 +65,16 @@ SYMBOLS = [
     "knhip_fvec_batch_4", "knhip_typed_vec_ny", "knhip_typed_vec_batch_4", "knhip_ivec_ny",
     "knhip_select_ordered_device", "knhip_index_calc_dist", "knhip_index_calc_dist_device",
     "knhip_iter_create", "knhip_iter_next", "knhip_iter_next_all", "knhip_iter_has_next", "knhip_iter_stats", "knhip_iter_destroy",
+    "knhip_index_prepare", "knhip_index_prepare_bytes", "knhip_index_prepared",
 ]
+
+# `uses` of a PrepareShape (KNHIP_PREP_* of include/knhip.h): what the index is prepared for
+PREP_SEARCH, PREP_RANGE, PREP_ITER, PREP_GET_VECTORS, PREP_CALC_DIST = 1, 2, 4, 8, 16
+
+
+class PrepareShape(C.Structure):
+    """knhip_prepare_shape: a search of nq queries for k results over nprobe lists, with or without a bitset"""
+    _fields_ = [("nq", C.c_int64), ("k", C.c_int32), ("nprobe", C.c_int32), ("with_bitset", C.c_int32), ("uses", C.c_int32)]
 
 
 # element type an IVF_FLAT index keeps its rows in on the device (knhip_index_set_row_type; the host boundary stays fp32)
@@ -216,6 +225,10 @@ def load():
         getattr(L, f).restype = i64
     L.knhip_search_refine_rows.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, i64, vp, vp]
     L.knhip_refine_rows_device.argtypes = [i32, vp, i64, vp, i64, vp, i32, i32, vp, vp, vp]
+    if hasattr(L, "knhip_index_prepare"):  # (as for the iterator: a KNHIP_LIB library may predate it)
+        L.knhip_index_prepare.argtypes = [vp, C.POINTER(PrepareShape), i32]
+        L.knhip_index_prepare_bytes.argtypes = [vp, C.POINTER(PrepareShape), i32, C.POINTER(C.c_int64)]
+        L.knhip_index_prepared.argtypes = [vp]
     L.knhip_profile_enable.argtypes = [vp, C.c_int]
     L.knhip_profile_reset.argtypes = [vp]
     L.knhip_profile_get.argtypes = [vp, C.POINTER(StageTimes)]

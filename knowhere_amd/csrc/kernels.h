@@ -368,6 +368,7 @@ hipError_t launch_pqd_index_prep(const float4* cb, const float* centroids, int64
 // per batch: qh16: nq * 128 halves; qd: nq * 4 floats = {||q||_1, B_q, eps_base, 2 B_q}
 hipError_t launch_pqd_query_prep(const float* queries, const float4* cb, const float* cst, int64_t nq, bool is_l2,
                                  float pabs_max, void* qh16, float* qd, hipStream_t s);
+hipError_t pqd_prepare_launches(); // (once per index, before its first launch_pqd: the kernels' dynamic LDS size)
 hipError_t launch_pqd(const MScanArgs& a, bool is_l2, int64_t units_bound, hipStream_t s);
 
 bool pqf_supports(int M, int d);

@@ -169,27 +169,98 @@ int maybe_build_precomp(knhip_index* idx) {
     return KNHIP_OK;
 }
 
+// ---- layouts built on first use ------------------------------------------------------------------------------------------
+// Every such layout has a *_launch function (idx->mu held by the caller) that allocates it and enqueues its kernels on the
+// stream of a LayoutBuild, and becomes ready in layouts_finish: one synchronisation, then the host-side scalars (largest
+// norm, largest |term 2| sum) are read back.  The lazy builders (ensure_*, build_pq_skew: a search's first use) run one
+// layout on the default stream; knhip_index_prepare runs all it needs on one stream of its own.
+struct LayoutBuild {
+    hipStream_t s = nullptr;                        // null: the default stream, drained with the device (the lazy builders)
+    unsigned launched = 0;                          // KN_LAY_* whose kernels are enqueued
+    std::vector<std::vector<int64_t>> keep;         // host arrays an asynchronous copy still reads
+    std::vector<std::unique_ptr<DevBuf>> scratch;   // device scratch the enqueued kernels still use
+    bool done(unsigned bit, bool ready) const { return ready || (launched & bit) != 0; }
+};
+
+static int64_t sum_blocks_r(const knhip_index* idx) {
+    int64_t t = 0;
+    for (int64_t l = 0; l < idx->nlist; l++) {
+        t += pq_stream16r_blocks(idx->h_list_len[l]);
+    }
+    return t;
+}
+static int64_t sum_blocks_skew(const knhip_index* idx) {
+    int64_t t = 0;
+    for (int64_t l = 0; l < idx->nlist; l++) {
+        t += pq_skew_blocks(idx->h_list_len[l], idx->desc.pq_m);
+    }
+    return t;
+}
+static size_t dev_alloc_bytes(size_t n) { return n == 0 ? 16 : n; } // (DevBuf::alloc)
+
 // IVF_PQ: the skewed code layout of the systolic kernel (pq_scan.hip), from the canonical AoS codes
-int build_pq_skew(const knhip_index* cidx) {
-    knhip_index* idx = const_cast<knhip_index*>(cidx);
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (idx->skew_ready) {
+static int skew_launch(knhip_index* idx, LayoutBuild& b) {
+    if (b.done(KN_LAY_SKEW, idx->skew_ready)) {
         return KNHIP_OK;
     }
     const int M = idx->desc.pq_m;
-    const int64_t nlist = idx->nlist;
-    std::vector<int64_t> blk_off(nlist + 1, 0);
-    for (int64_t l = 0; l < nlist; l++) {
-        blk_off[l + 1] = blk_off[l] + pq_skew_blocks(idx->h_list_len[l], M);
-    }
-    HIP_TRY(idx->rows.alloc((size_t)blk_off[nlist] * M * sizeof(uint4)));
+    HIP_TRY(idx->rows.alloc((size_t)sum_blocks_skew(idx) * M * sizeof(uint4)));
     HIP_TRY(launch_pq_skew_codes(idx->codes_aos.as<uint8_t>(), idx->d_list_row_off.as<int64_t>(),
-                                 idx->d_list_len.as<int64_t>(), idx->d_list_blk_off.as<int64_t>(), nlist, M,
-                                 idx->rows.as<uint4>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    idx->skew_ready = true;
+                                 idx->d_list_len.as<int64_t>(), idx->d_list_blk_off.as<int64_t>(), idx->nlist, M,
+                                 idx->rows.as<uint4>(), b.s));
+    b.launched |= KN_LAY_SKEW;
     return KNHIP_OK;
 }
+
+// the enqueued layouts become ready: one synchronisation, the scalars the host keeps, the flags
+static int layouts_finish(knhip_index* idx, LayoutBuild& b) {
+    if (b.launched == 0 && b.keep.empty() && b.scratch.empty()) {
+        return KNHIP_OK;
+    }
+    const unsigned got = b.launched;
+    b.launched = 0;
+    HIP_TRY(b.s != nullptr ? hipStreamSynchronize(b.s) : hipDeviceSynchronize());
+    b.keep.clear();
+    b.scratch.clear();
+    if (got & KN_LAY_XNORM) {
+        const float* xmax = idx->xnorm.as<float>() + std::max<int64_t>(idx->total_blk, 1) * 64;
+        HIP_TRY(hipMemcpy(&idx->xnorm_max, xmax, sizeof(float), hipMemcpyDeviceToHost));
+        idx->xnorm_ready = true;
+    }
+    if (got & KN_LAY_PSUM) {
+        idx->pabs_max = 0.f;
+        if (idx->is_l2) {
+            const float* bits = idx->psum.as<float>() + (idx->psum.bytes / sizeof(float) - 4);
+            HIP_TRY(hipMemcpy(&idx->pabs_max, bits, sizeof(float), hipMemcpyDeviceToHost));
+        }
+        idx->psum_ready = true;
+    }
+    if (got & KN_LAY_BF_SPLIT) {
+        // (the largest norm, reduced on the device: bf_norm_max_kernel)
+        const float* mx = idx->bf_norm.as<float>() + std::max<int64_t>(idx->ntotal, 1);
+        HIP_TRY(hipMemcpy(&idx->bf_norm_max, mx, sizeof(float), hipMemcpyDeviceToHost));
+        idx->bf_split_ready = true;
+    }
+    idx->pqf_ready = idx->pqf_ready || (got & KN_LAY_PQF) != 0;
+    idx->pqd_ready = idx->pqd_ready || (got & KN_LAY_PQD) != 0;
+    idx->pqi_ready = idx->pqi_ready || (got & KN_LAY_PQI) != 0;
+    idx->skew_ready = idx->skew_ready || (got & KN_LAY_SKEW) != 0;
+    idx->idmap_ready = idx->idmap_ready || (got & KN_LAY_IDMAP) != 0;
+    return KNHIP_OK;
+}
+
+// a lazy builder: one layout on the default stream, ready when it returns
+template <class F>
+static int build_one_layout(const knhip_index* cidx, F launch) {
+    knhip_index* idx = const_cast<knhip_index*>(cidx);
+    std::lock_guard<std::mutex> lk(idx->mu);
+    LayoutBuild b;
+    const int rc = launch(idx, b);
+    const int rc2 = layouts_finish(idx, b); // (what was enqueued before a failure is drained and kept)
+    return rc != KNHIP_OK ? rc : rc2;
+}
+
+int build_pq_skew(const knhip_index* idx) { return build_one_layout(idx, skew_launch); }
 
 // flat / SQ8 indexes above this many code bytes keep only the interleaved layout (KNHIP_AOS_KEEP_MB overrides; tests
 // set it to 0 to exercise the rebuild path)
@@ -251,6 +322,12 @@ int build_list_layout(knhip_index* idx, const std::vector<int64_t>& list_off, co
         idx->rows_r.release();
         idx->psum.release();
         idx->psum_s.release();
+        // (knhip_index_device_bytes counts only what belongs to the current lists: the next first use rebuilds these)
+        idx->xnorm.release();
+        idx->d_list_blk_off_r.release();
+        idx->pqd_cb16.release();
+        idx->pqd_st.release();
+        idx->prepared = false;
     }
     for (int64_t l = 0; l < nlist; l++) {
         idx->h_list_len[l] = list_off[l + 1] - list_off[l];
@@ -366,123 +443,110 @@ int ensure_aos(const knhip_index* cidx) {
 }
 
 // ||x||^2 per stored row (fp32 rows: any metric, for the error bound; SQ8: L2 only), built on first use
-int ensure_mscan_norms(const knhip_index* idx) {
-    const int64_t total_blk = idx->total_blk;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (idx->xnorm_ready) {
+static int xnorm_launch(knhip_index* idx, LayoutBuild& b) {
+    if (b.done(KN_LAY_XNORM, idx->xnorm_ready)) {
         return KNHIP_OK;
     }
+    const int64_t total_blk = idx->total_blk;
     HIP_TRY(idx->xnorm.alloc((size_t)std::max<int64_t>(total_blk, 1) * 64 * sizeof(float) + 16));
     float* xn = idx->xnorm.as<float>();
     float* xmax = xn + std::max<int64_t>(total_blk, 1) * 64;
     if (idx->desc.kind == KNHIP_IVF_FLAT) {
-        HIP_TRY(launch_ms_block_norms(idx->rows.as<float4>(), total_blk, row_nchunk(idx->d, idx->row_type), xn, xmax, nullptr,
+        HIP_TRY(launch_ms_block_norms(idx->rows.as<float4>(), total_blk, row_nchunk(idx->d, idx->row_type), xn, xmax, b.s,
                                       idx->row_type));
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(&idx->xnorm_max, xmax, sizeof(float), hipMemcpyDeviceToHost));
     } else {
         HIP_TRY(launch_ms_sq8_norms(idx->rows.as<uint4>(), total_blk, sq_nchunk16(idx->d, idx->sq_bits), idx->d,
-                                    idx->sq_trained.as<float>(), xn, xmax, nullptr, idx->sq_bits));
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(&idx->xnorm_max, xmax, sizeof(float), hipMemcpyDeviceToHost));
+                                    idx->sq_trained.as<float>(), xn, xmax, b.s, idx->sq_bits));
     }
-    idx->xnorm_ready = true;
+    b.launched |= KN_LAY_XNORM;
     return KNHIP_OK;
 }
+int ensure_mscan_norms(const knhip_index* idx) { return build_one_layout(idx, xnorm_launch); }
 
 // IVF-PQ prefilter, every form and the sample pass: per-vector term-2 sums (+ the block offsets they are indexed by), from the
 // canonical AoS codes
-int ensure_psum(const knhip_index* idx) {
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (idx->psum_ready) {
+static int psum_launch(knhip_index* idx, LayoutBuild& b) {
+    if (b.done(KN_LAY_PSUM, idx->psum_ready)) {
         return KNHIP_OK;
     }
     const int64_t nlist = idx->nlist;
-    std::vector<int64_t> off(nlist + 1, 0);
+    b.keep.emplace_back((size_t)nlist + 1, 0);
+    std::vector<int64_t>& off = b.keep.back();
     for (int64_t l = 0; l < nlist; l++) {
         off[l + 1] = off[l] + pq_stream16r_blocks(idx->h_list_len[l]);
     }
     HIP_TRY(idx->d_list_blk_off_r.alloc((size_t)(nlist + 1) * sizeof(int64_t)));
-    HIP_TRY(hipMemcpy(idx->d_list_blk_off_r.p, off.data(), (size_t)(nlist + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    idx->pabs_max = 0.f;
+    HIP_TRY(hipMemcpyAsync(idx->d_list_blk_off_r.p, off.data(), (size_t)(nlist + 1) * sizeof(int64_t), hipMemcpyHostToDevice, b.s));
     if (idx->is_l2) {
         const size_t npos = (size_t)std::max<int64_t>(off[nlist], 1) * 16; // 16 vector positions per block
         HIP_TRY(idx->psum.alloc((npos + 4) * sizeof(float)));
-        HIP_TRY(hipMemset(idx->psum.p, 0, (npos + 4) * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(idx->psum.p, 0, (npos + 4) * sizeof(float), b.s));
         uint32_t* bits = reinterpret_cast<uint32_t*>(idx->psum.as<float>() + npos);
         HIP_TRY(launch_pq_psum(idx->codes_aos.as<uint8_t>(), idx->d_list_row_off.as<int64_t>(),
                                idx->d_list_len.as<int64_t>(), idx->d_list_blk_off_r.as<int64_t>(), nlist,
-                               idx->precomp_t.as<float>(), idx->psum.as<float>(), bits, nullptr));
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(&idx->pabs_max, bits, sizeof(float), hipMemcpyDeviceToHost));
+                               idx->precomp_t.as<float>(), idx->psum.as<float>(), bits, b.s));
     }
-    HIP_TRY(hipDeviceSynchronize());
-    idx->psum_ready = true;
+    b.launched |= KN_LAY_PSUM;
     return KNHIP_OK;
 }
+int ensure_psum(const knhip_index* idx) { return build_one_layout(idx, psum_launch); }
 
 // ... the half form: + the rotated token stream
-int ensure_pqf(const knhip_index* idx) {
-    if (int rc = ensure_psum(idx)) return rc;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (idx->pqf_ready) {
+static int pqf_launch(knhip_index* idx, LayoutBuild& b) {
+    if (int rc = psum_launch(idx, b)) return rc;
+    if (b.done(KN_LAY_PQF, idx->pqf_ready)) {
         return KNHIP_OK;
     }
-    const int64_t nblk = idx->nlist > 0 ? [&] {
-        int64_t t = 0;
-        for (int64_t l = 0; l < idx->nlist; l++) t += pq_stream16r_blocks(idx->h_list_len[l]);
-        return t;
-    }() : 0;
+    const int64_t nblk = sum_blocks_r(idx);
     HIP_TRY(idx->rows_r.alloc((size_t)std::max<int64_t>(nblk, 1) * 64 * sizeof(uint4)));
     HIP_TRY(launch_pq_stream16r(idx->codes_aos.as<uint8_t>(), idx->d_list_row_off.as<int64_t>(),
                                 idx->d_list_len.as<int64_t>(), idx->d_list_blk_off_r.as<int64_t>(), idx->nlist,
-                                idx->rows_r.as<uint4>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    idx->pqf_ready = true;
+                                idx->rows_r.as<uint4>(), b.s));
+    b.launched |= KN_LAY_PQF;
     return KNHIP_OK;
 }
+int ensure_pqf(const knhip_index* idx) { return build_one_layout(idx, pqf_launch); }
 
 // ... the decode form (pq_decode.hip): the codebook as halves, the index's scales, the rows' start values -psum SC / 2.  No
 // token stream: the kernel reads the canonical AoS codes as they lie
-int ensure_pqd(const knhip_index* idx) {
-    if (int rc = ensure_psum(idx)) return rc;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (idx->pqd_ready) {
+static int pqd_launch(knhip_index* idx, LayoutBuild& b) {
+    if (int rc = psum_launch(idx, b)) return rc;
+    if (b.done(KN_LAY_PQD, idx->pqd_ready)) {
         return KNHIP_OK;
     }
+    HIP_TRY(pqd_prepare_launches()); // (the decode kernels' LDS size, once per index instead of once per launch)
     HIP_TRY(idx->pqd_cb16.alloc((size_t)32 * 256 * 4 * 2));
     HIP_TRY(idx->pqd_st.alloc(16 * sizeof(float)));
     const int64_t npsum = idx->is_l2 ? (int64_t)(idx->psum.bytes / sizeof(float)) - 4 : 0;
     if (npsum > 0) {
         // (+ 64: the scan's last 32-row tile of the last list reads up to 16 entries past the list's 16-row blocks)
         HIP_TRY(idx->psum_s.alloc((size_t)(npsum + 64) * sizeof(float)));
-        HIP_TRY(hipMemset(idx->psum_s.p, 0, (size_t)(npsum + 64) * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(idx->psum_s.p, 0, (size_t)(npsum + 64) * sizeof(float), b.s));
     }
     HIP_TRY(launch_pqd_index_prep(idx->cb.as<float4>(), idx->centroids.as<float>(), idx->nlist * (int64_t)idx->d,
                                   idx->pqd_cb16.p, idx->pqd_st.as<float>(),
                                   reinterpret_cast<uint32_t*>(idx->pqd_st.as<float>() + 8), idx->psum.as<float>(), npsum,
-                                  idx->psum_s.as<float>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    idx->pqd_ready = true;
+                                  idx->psum_s.as<float>(), b.s));
+    b.launched |= KN_LAY_PQD;
     return KNHIP_OK;
 }
+int ensure_pqd(const knhip_index* idx) { return build_one_layout(idx, pqd_launch); }
 
 // token stream of the integer form of the prefilter (same block offsets as the half-precision stream)
-int ensure_pqi(const knhip_index* idx) {
-    if (int rc = ensure_pqf(idx)) return rc;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (idx->pqi_ready) {
+static int pqi_launch(knhip_index* idx, LayoutBuild& b) {
+    if (int rc = pqf_launch(idx, b)) return rc;
+    if (b.done(KN_LAY_PQI, idx->pqi_ready)) {
         return KNHIP_OK;
     }
     const int64_t nblk = idx->rows_r.bytes / (64 * sizeof(uint4));
     HIP_TRY(idx->rows_i.alloc((size_t)std::max<int64_t>(nblk, 1) * 64 * sizeof(uint4)));
     HIP_TRY(launch_pq_stream16i(idx->codes_aos.as<uint8_t>(), idx->d_list_row_off.as<int64_t>(),
                                 idx->d_list_len.as<int64_t>(), idx->d_list_blk_off_r.as<int64_t>(), idx->nlist,
-                                idx->rows_i.as<uint4>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    idx->pqi_ready = true;
+                                idx->rows_i.as<uint4>(), b.s));
+    b.launched |= KN_LAY_PQI;
     return KNHIP_OK;
 }
+int ensure_pqi(const knhip_index* idx) { return build_one_layout(idx, pqi_launch); }
 
 Workspace* acquire_ws(const knhip_index* idx, void* stream_key, bool pooled_by_stream) {
     std::lock_guard<std::mutex> lk(idx->mu);
@@ -518,28 +582,76 @@ void release_ws(const knhip_index* idx, Workspace* w) {
 // 131072 rows (the bound kernel holds up to 4096 group minima per query); the chunks' top-k lists are merged as the row
 // scan's are.  Taken when no bitset is given (the prefilter cannot count filtered rows), the metric is plain L2 / IP, and the
 // batch is large enough to pay for splitting the queries.
-int ensure_bf_split(const knhip_index* idx) {
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (idx->bf_split_ready) {
+// the largest norm of the rows, on the device: *out_bits = max over v[i] > 0 of the pattern of v[i], 0 if there is none
+// (*out_bits zeroed by the caller).  The patterns of positive floats order as the values do, +inf included, and the maximum
+// does not depend on the order it is taken in: the same 32 bits as a host loop `mx = v > mx ? v : mx` from 0 -- a NaN norm
+// never raises it (such a row fails every certificate it could decide)
+__global__ void bf_norm_max_kernel(const float* __restrict__ v, int64_t n, uint32_t* __restrict__ out_bits) {
+    uint32_t m = 0u;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float x = v[i];
+        if (x > 0.f) { // (false for a NaN)
+            const uint32_t u = __float_as_uint(x);
+            m = u > m ? u : m;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t t = __shfl_xor(m, o);
+        m = t > m ? t : m;
+    }
+    if ((threadIdx.x & 63) == 0 && m != 0u) {
+        atomicMax(out_bits, m);
+    }
+}
+
+static int bf_split_launch(knhip_index* idx, LayoutBuild& b) {
+    if (b.done(KN_LAY_BF_SPLIT, idx->bf_split_ready)) {
         return KNHIP_OK;
     }
-    const int64_t nb = idx->ntotal;
+    const int64_t nb = idx->ntotal, nrow = std::max<int64_t>(nb, 1);
     const int nslab = coarse_bf16_slabs(idx->d);
-    HIP_TRY(idx->rows_bs.alloc((size_t)std::max<int64_t>(nb, 1) * nslab * 128));
-    HIP_TRY(idx->bf_norm.alloc((size_t)std::max<int64_t>(nb, 1) * sizeof(float)));
-    HIP_TRY(launch_coarse_bf16_split(idx->codes_aos.as<float>(), nb, idx->d, idx->rows_bs.p, nullptr));
-    HIP_TRY(launch_row_norms(idx->codes_aos.as<float>(), nb, idx->d, idx->bf_norm.as<float>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    std::vector<float> h((size_t)nb);
-    HIP_TRY(hipMemcpy(h.data(), idx->bf_norm.p, h.size() * sizeof(float), hipMemcpyDeviceToHost));
-    float mx = 0.f;
-    for (float v : h) {
-        mx = v > mx ? v : mx; // (a NaN norm never raises it: such a row fails every certificate it could decide)
+    HIP_TRY(idx->rows_bs.alloc((size_t)nrow * nslab * 128));
+    HIP_TRY(idx->bf_norm.alloc((size_t)nrow * sizeof(float) + 16)); // (+ the largest norm, behind the rows' norms)
+    HIP_TRY(launch_coarse_bf16_split(idx->codes_aos.as<float>(), nb, idx->d, idx->rows_bs.p, b.s));
+    HIP_TRY(launch_row_norms(idx->codes_aos.as<float>(), nb, idx->d, idx->bf_norm.as<float>(), b.s));
+    uint32_t* mx = reinterpret_cast<uint32_t*>(idx->bf_norm.as<float>() + nrow);
+    HIP_TRY(hipMemsetAsync(mx, 0, sizeof(uint32_t), b.s));
+    if (nb > 0) {
+        const unsigned grid = (unsigned)std::min<int64_t>((nb + 255) / 256, 1024);
+        hipLaunchKernelGGL(bf_norm_max_kernel, dim3(grid), dim3(256), 0, b.s, idx->bf_norm.as<float>(), nb, mx);
+        HIP_TRY(hipGetLastError());
     }
-    idx->bf_norm_max = mx;
-    idx->bf_split_ready = true;
+    b.launched |= KN_LAY_BF_SPLIT;
     return KNHIP_OK;
 }
+int ensure_bf_split(const knhip_index* idx) { return build_one_layout(idx, bf_split_launch); }
+
+// IVF-Flat direct map (knhip_index_get_vectors, knhip_index_calc_dist): ids sorted once with the column of their row in the
+// interleaved store (16 bytes per vector, against the 4 d bytes of a second copy of the raw rows the node used to keep for
+// this call: ADVICE round 2)
+static int idmap_launch(knhip_index* idx, LayoutBuild& b) {
+    if (b.done(KN_LAY_IDMAP, idx->idmap_ready)) {
+        return KNHIP_OK;
+    }
+    const int64_t n = idx->ntotal;
+    if (n > 0) {
+        const size_t tb = idmap_sort_tmp_bytes(n);
+        b.scratch.emplace_back(new DevBuf());
+        DevBuf& col_tmp = *b.scratch.back();
+        b.scratch.emplace_back(new DevBuf());
+        DevBuf& tmp = *b.scratch.back();
+        HIP_TRY(col_tmp.alloc((size_t)n * sizeof(int64_t)));
+        HIP_TRY(tmp.alloc(tb));
+        HIP_TRY(idx->idmap_ids.alloc((size_t)n * sizeof(int64_t)));
+        HIP_TRY(idx->idmap_col.alloc((size_t)n * sizeof(int64_t)));
+        HIP_TRY(launch_idmap_build(idx->ids.as<int64_t>(), idx->d_list_row_off.as<int64_t>(),
+                                   idx->d_list_blk_off.as<int64_t>(), idx->nlist, n, col_tmp.as<int64_t>(),
+                                   idx->idmap_ids.as<int64_t>(), idx->idmap_col.as<int64_t>(), tmp.p, tb, b.s));
+    }
+    b.launched |= KN_LAY_IDMAP;
+    return KNHIP_OK;
+}
+int ensure_idmap(const knhip_index* idx) { return build_one_layout(idx, idmap_launch); }
 
 // what knhip_profile_get reports of the last search
 void note_route(const knhip_index* idx, bool bf_mfma, int pq_form, bool rank0_phase, int64_t items_bound) {
@@ -739,6 +851,8 @@ int knhip_index_set_sq(knhip_index* idx, const float* vmin, const float* vdiff) 
     if (int rc = upload(idx->sq_trained, t.data(), t.size() * sizeof(float))) return rc;
     idx->has_sq = true;
     idx->xnorm_ready = false;
+    idx->xnorm.release();
+    idx->prepared = false;
     return KNHIP_OK;
 }
 
@@ -940,6 +1054,7 @@ int add_vectors_common(knhip_index* idx, int64_t n, const float* d_x, const int6
     idx->bf_split_ready = false;
     idx->rows_bs.release();
     idx->bf_norm.release();
+    idx->prepared = false;
     {
         const EnvLayout env = env_layout(); // (KNHIP_COARSE: the switch of the stage whose machinery this is)
         idx->bf_mfma = !env.bf_exact && !env.coarse_given;
@@ -999,6 +1114,218 @@ int64_t knhip_index_last_range_ranks(const knhip_index* idx) {
 
 int knhip_index_uses_precomputed_table(const knhip_index* idx) {
     return idx ? idx->use_precomp : 0;
+}
+
+} // extern "C"
+
+// ---- knhip_index_prepare: the layouts built on first use, up front --------------------------------------------------------
+namespace knhip_host {
+
+// what is asked for, checked: the KN_LAY_* bits the given shapes (nshapes == 0: any shape) would build lazily on this index
+static int prepare_layouts(const knhip_index* idx, const knhip_prepare_shape* shapes, int32_t nshapes, unsigned* out) {
+    *out = 0;
+    if (nshapes < 0 || (nshapes > 0 && shapes == nullptr)) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "prepare: nshapes shapes are needed (0: any shape)");
+    }
+    const int all_uses = KNHIP_PREP_SEARCH | KNHIP_PREP_RANGE | KNHIP_PREP_ITER | KNHIP_PREP_GET_VECTORS | KNHIP_PREP_CALC_DIST;
+    for (int32_t i = 0; i < nshapes; i++) {
+        const knhip_prepare_shape& h = shapes[i];
+        const bool searches = h.uses == 0 || (h.uses & KNHIP_PREP_SEARCH) != 0;
+        if ((h.uses & ~all_uses) != 0) {
+            return fail(KNHIP_ERR_INVALID_ARGS, "prepare: shape " + std::to_string(i) + " has an unknown bit in `uses`");
+        }
+        if (h.nq < 0 || (h.with_bitset != 0 && h.with_bitset != 1)) {
+            return fail(KNHIP_ERR_INVALID_ARGS, "prepare: shape " + std::to_string(i) + ": nq must be >= 0 and with_bitset 0 or 1");
+        }
+        if (searches && (h.k <= 0 || h.k > KNHIP_MAX_K || (idx->desc.kind != KNHIP_BRUTE_FORCE && h.nprobe <= 0))) {
+            return fail(KNHIP_ERR_INVALID_ARGS, "prepare: shape " + std::to_string(i) + ": a search needs 0 < k <= 16384 and nprobe > 0");
+        }
+    }
+    const int kind = idx->desc.kind;
+    if (!idx->has_data || (kind != KNHIP_BRUTE_FORCE && !idx->has_coarse)) {
+        return KNHIP_OK; // (nothing to lay out yet: the next Add invalidates anyway)
+    }
+    unsigned need = 0;
+    // one search as knhip_search* runs it: batches of query_batch() queries (and the remainder), k + 1 results where the
+    // boundary rule applies, nprobe clamped to nlist; 1024 < k: the large-k path, which reads the lists as every index holds them
+    auto one_search = [&](int64_t nq, int k, int nprobe, bool bitset) {
+        if (nq <= 0 || k > KN_MAX_K) {
+            return;
+        }
+        nprobe = kind == KNHIP_BRUTE_FORCE ? nprobe : (int)std::min<int64_t>(nprobe, idx->nlist);
+        const int64_t qb = query_batch(idx, nq, k, nprobe);
+        const int ks = knhip_ties_rule_applies(kind, k) ? k + 1 : k;
+        need |= search_batch_layouts(idx, std::min(qb, nq), ks, nprobe, bitset);
+        if (nq > qb && nq % qb != 0) {
+            need |= search_batch_layouts(idx, nq % qb, ks, nprobe, bitset);
+        }
+    };
+    if (nshapes == 0) {
+        // any shape: few and many queries, k on both sides of the 4-query kernel's limit and at the largest, every list probed, with
+        // and without a bitset -- every side of every threshold of plan_search -- and every use
+        for (int64_t nq : {(int64_t)4, (int64_t)1 << 16}) {
+            for (int k : {10, 200, KN_MAX_K}) {
+                for (int bitset = 0; bitset < 2; bitset++) {
+                    one_search(nq, k, kind == KNHIP_BRUTE_FORCE ? 1 : (int)idx->nlist, bitset != 0);
+                }
+            }
+        }
+        need |= kind == KNHIP_IVF_FLAT ? KN_LAY_IDMAP : 0u;
+    }
+    for (int32_t i = 0; i < nshapes; i++) {
+        const knhip_prepare_shape& h = shapes[i];
+        if (h.uses == 0 || (h.uses & KNHIP_PREP_SEARCH) != 0) {
+            one_search(h.nq, h.k, h.nprobe, h.with_bitset != 0);
+        }
+        if ((h.uses & (KNHIP_PREP_GET_VECTORS | KNHIP_PREP_CALC_DIST)) != 0 && kind == KNHIP_IVF_FLAT) {
+            need |= KN_LAY_IDMAP;
+        }
+    }
+    // (a form's layouts rest on the shared ones)
+    if (need & KN_LAY_PQI) need |= KN_LAY_PQF;
+    if (need & (KN_LAY_PQF | KN_LAY_PQD)) need |= KN_LAY_PSUM;
+    *out = need;
+    return KNHIP_OK;
+}
+
+struct LayoutInfo {
+    unsigned bit;
+    const char* name;
+    bool ready;
+    int64_t bytes, held; // what the layout's buffers will hold once built (a closed form of the list lengths), what they hold now
+};
+
+// the layouts in the order prepare builds them (the shared ones first)
+static std::vector<LayoutInfo> layout_table(const knhip_index* idx) {
+    const int64_t nlist = idx->nlist, nb = idx->ntotal;
+    const bool pq = idx->desc.kind == KNHIP_IVF_PQ;
+    const int64_t nblk_r = pq ? sum_blocks_r(idx) : 0;
+    const int64_t npos = std::max<int64_t>(nblk_r, 1) * 16;
+    const int64_t stream_bytes = std::max<int64_t>(nblk_r, 1) * 64 * (int64_t)sizeof(uint4);
+    auto held = [](std::initializer_list<const DevBuf*> l) {
+        int64_t t = 0;
+        for (const DevBuf* b : l) t += (int64_t)b->bytes;
+        return t;
+    };
+    std::vector<LayoutInfo> t;
+    t.push_back({KN_LAY_XNORM, "row norms of the prefilter (xnorm)", idx->xnorm_ready,
+                 std::max<int64_t>(idx->total_blk, 1) * 64 * 4 + 16, held({&idx->xnorm})});
+    t.push_back({KN_LAY_PSUM, "IVF-PQ term-2 sums and their block offsets (psum)", idx->psum_ready,
+                 (nlist + 1) * 8 + (idx->is_l2 ? (npos + 4) * 4 : 0), held({&idx->d_list_blk_off_r, &idx->psum})});
+    t.push_back({KN_LAY_PQD, "IVF-PQ decode form: half codebook, scales, start values (pqd)", idx->pqd_ready,
+                 32 * 256 * 4 * 2 + 64 + (idx->is_l2 ? (npos + 64) * 4 : 0), held({&idx->pqd_cb16, &idx->pqd_st, &idx->psum_s})});
+    t.push_back({KN_LAY_PQF, "IVF-PQ half-table token stream (pqf)", idx->pqf_ready, stream_bytes, held({&idx->rows_r})});
+    t.push_back({KN_LAY_PQI, "IVF-PQ int8-table token stream (pqi)", idx->pqi_ready, stream_bytes, held({&idx->rows_i})});
+    t.push_back({KN_LAY_SKEW, "IVF-PQ skewed code layout (k > 128)", idx->skew_ready,
+                 pq ? (int64_t)dev_alloc_bytes((size_t)sum_blocks_skew(idx) * idx->desc.pq_m * sizeof(uint4)) : 0,
+                 held({&idx->rows})});
+    t.push_back({KN_LAY_BF_SPLIT, "BRUTE_FORCE split-bf16 operand rows and norms (bf_split)", idx->bf_split_ready,
+                 std::max<int64_t>(nb, 1) * coarse_bf16_slabs(idx->d) * 128 + std::max<int64_t>(nb, 1) * 4 + 16,
+                 held({&idx->rows_bs, &idx->bf_norm})});
+    t.push_back({KN_LAY_IDMAP, "IVF-Flat direct map (idmap)", idx->idmap_ready, nb > 0 ? 2 * nb * 8 : 0,
+                 held({&idx->idmap_ids, &idx->idmap_col})});
+    return t;
+}
+
+// buffers of a layout that did not become ready (an allocation failed half way): not index memory
+static void release_unready(knhip_index* idx, unsigned bit) {
+    switch (bit) {
+        case KN_LAY_XNORM: idx->xnorm.release(); break;
+        case KN_LAY_PSUM: idx->d_list_blk_off_r.release(); idx->psum.release(); break;
+        case KN_LAY_PQD: idx->pqd_cb16.release(); idx->pqd_st.release(); idx->psum_s.release(); break;
+        case KN_LAY_PQF: idx->rows_r.release(); break;
+        case KN_LAY_PQI: idx->rows_i.release(); break;
+        case KN_LAY_SKEW: idx->rows.release(); break;
+        case KN_LAY_BF_SPLIT: idx->rows_bs.release(); idx->bf_norm.release(); break;
+        case KN_LAY_IDMAP: idx->idmap_ids.release(); idx->idmap_col.release(); break;
+    }
+}
+
+static int launch_layout(knhip_index* idx, unsigned bit, LayoutBuild& b) {
+    switch (bit) {
+        case KN_LAY_XNORM: return xnorm_launch(idx, b);
+        case KN_LAY_PSUM: return psum_launch(idx, b);
+        case KN_LAY_PQD: return pqd_launch(idx, b);
+        case KN_LAY_PQF: return pqf_launch(idx, b);
+        case KN_LAY_PQI: return pqi_launch(idx, b);
+        case KN_LAY_SKEW: return skew_launch(idx, b);
+        case KN_LAY_BF_SPLIT: return bf_split_launch(idx, b);
+        case KN_LAY_IDMAP: return idmap_launch(idx, b);
+    }
+    return KNHIP_OK;
+}
+
+} // namespace knhip_host
+
+extern "C" {
+
+int knhip_index_prepare_bytes(const knhip_index* idx, const knhip_prepare_shape* shapes, int32_t nshapes, int64_t* extra_bytes) {
+    if (int rc = check_index(idx)) return rc;
+    if (!extra_bytes) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "prepare_bytes: null output");
+    }
+    *extra_bytes = 0;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    unsigned need = 0;
+    if (int rc = prepare_layouts(idx, shapes, nshapes, &need)) return rc;
+    int64_t extra = 0;
+    for (const LayoutInfo& l : layout_table(idx)) {
+        if ((need & l.bit) != 0 && !l.ready) {
+            extra += l.bytes - l.held;
+        }
+    }
+    *extra_bytes = extra;
+    return KNHIP_OK;
+}
+
+int knhip_index_prepare(knhip_index* idx, const knhip_prepare_shape* shapes, int32_t nshapes) {
+    if (int rc = check_index(idx)) return rc;
+    DeviceGuard g(idx->desc.device);
+    std::lock_guard<std::mutex> lk(idx->mu);
+    unsigned need = 0;
+    if (int rc = prepare_layouts(idx, shapes, nshapes, &need)) return rc;
+    const std::vector<LayoutInfo> table = layout_table(idx);
+    bool work = false;
+    for (const LayoutInfo& l : table) {
+        work = work || ((need & l.bit) != 0 && !l.ready);
+    }
+    if (!work) { // (idempotent: nothing to launch, no stream, no synchronisation)
+        idx->prepared = true;
+        return KNHIP_OK;
+    }
+    LayoutBuild b;
+    HIP_TRY(hipStreamCreateWithFlags(&b.s, hipStreamNonBlocking));
+    int rc = KNHIP_OK;
+    for (const LayoutInfo& l : table) {
+        if ((need & l.bit) == 0 || l.ready) {
+            continue;
+        }
+        rc = launch_layout(idx, l.bit, b);
+        if (rc != KNHIP_OK) {
+            // (what was enqueued before it is finished below and stays; the index is searchable: the lazy builders still work)
+            const std::string why = g_last_error;
+            (void)layouts_finish(idx, b);
+            release_unready(idx, l.bit);
+            rc = fail(rc, std::string("prepare: layout '") + l.name + "' of " + std::to_string(l.bytes) + " bytes: " + why);
+            break;
+        }
+    }
+    if (rc == KNHIP_OK) {
+        rc = layouts_finish(idx, b); // the one synchronisation
+    }
+    (void)hipStreamDestroy(b.s);
+    if (rc == KNHIP_OK) {
+        idx->prepared = true;
+    }
+    return rc;
+}
+
+int knhip_index_prepared(const knhip_index* idx) {
+    if (!idx) {
+        return 0;
+    }
+    std::lock_guard<std::mutex> lk(idx->mu);
+    return idx->prepared ? 1 : 0;
 }
 
 // (defined behind the range pass it reuses)
@@ -1241,31 +1568,6 @@ int knhip_search_refine_rows(const knhip_index* idx, const knhip_rows* rows, con
 }
 
 // rows of a brute-force index by id (GetVectorByIds): ids are row + id_offset
-// IVF-Flat: ids sorted once with the column of their row in the interleaved store (16 bytes per vector, against the
-// 4 d bytes of a second copy of the raw rows the node used to keep for this call: ADVICE round 2)
-static int ensure_idmap(const knhip_index* cidx) {
-    knhip_index* idx = const_cast<knhip_index*>(cidx);
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (idx->idmap_ready) {
-        return KNHIP_OK;
-    }
-    const int64_t n = idx->ntotal;
-    if (n > 0) {
-        DevBuf col_tmp, tmp;
-        const size_t tb = idmap_sort_tmp_bytes(n);
-        HIP_TRY(col_tmp.alloc((size_t)n * sizeof(int64_t)));
-        HIP_TRY(tmp.alloc(tb));
-        HIP_TRY(idx->idmap_ids.alloc((size_t)n * sizeof(int64_t)));
-        HIP_TRY(idx->idmap_col.alloc((size_t)n * sizeof(int64_t)));
-        HIP_TRY(launch_idmap_build(idx->ids.as<int64_t>(), idx->d_list_row_off.as<int64_t>(),
-                                   idx->d_list_blk_off.as<int64_t>(), idx->nlist, n, col_tmp.as<int64_t>(),
-                                   idx->idmap_ids.as<int64_t>(), idx->idmap_col.as<int64_t>(), tmp.p, tb, nullptr));
-        HIP_TRY(hipDeviceSynchronize());
-    }
-    idx->idmap_ready = true;
-    return KNHIP_OK;
-}
-
 int knhip_index_get_vectors(const knhip_index* idx, int64_t n, const int64_t* ids, float* out) {
     if (int rc = check_index(idx)) return rc;
     const int kind = idx->desc.kind;

@@ -996,6 +996,45 @@ int search_batch(const knhip_index* idx, Workspace* ws, const float* d_q, int64_
     return rc;
 }
 
+// ---- knhip_index_prepare: which of the layouts built on first use the routes above reach for a batch of this shape.  One
+// line per ensure_* / build_pq_skew call of this file, under the condition that guards it; where the guard of the IVF-PQ
+// prefilter decides after the sample pass (pq_choose_form), every outcome it can have for this index.
+unsigned search_batch_layouts(const knhip_index* idx, int64_t nq, int k, int nprobe, bool have_bitset) {
+    const SearchPlan plan = plan_search(idx, nq, k, nprobe, have_bitset, env_search());
+    const int kind = idx->desc.kind;
+    unsigned need = 0;
+    switch (plan.route) {
+        case Route::BfMfma: need |= KN_LAY_BF_SPLIT; break; // bf_mfma_batch
+        case Route::BfRows:
+        case Route::PqAny: break;
+        case Route::Exact:
+            if (kind == KNHIP_IVF_PQ && !plan.pq_v2) need |= KN_LAY_SKEW; // pq_exact_scan
+            break;
+        case Route::Prefilter:
+            if (kind != KNHIP_IVF_PQ) {
+                need |= KN_LAY_XNORM; // ms_common_args
+                break;
+            }
+            need |= KN_LAY_PSUM; // ms_common_args
+            {
+                // pq_choose_form: the second form (decode, or int8 when asked for) and when the half tables can still be taken
+                const bool want_dec = pqd_supports(idx->desc.pq_m, idx->d) && (idx->pqf_form == 0 || idx->pqf_form == 3);
+                const bool want2 = plan.pq_want_i8 || want_dec;
+                const int form2 = want_dec ? 3 : 2;
+                if (want_dec) need |= KN_LAY_PQD;
+                if (want2 && form2 == 2) need |= KN_LAY_PQI | KN_LAY_PQF;
+                const bool half_possible = idx->pqf_guard ? !(want2 && idx->pqf_form == form2) : !want2;
+                if (half_possible) need |= KN_LAY_PQF;
+                // the guard may abandon the batch to the exact kernels (pq_exact_scan); overflowed queries take
+                // exact_one_pair_items whatever the form
+                const bool may_abandon = idx->pqf_guard && !(want2 && idx->pqf_form == form2);
+                if (!plan.pq_q4_ok || (may_abandon && !plan.pq_v2)) need |= KN_LAY_SKEW;
+            }
+            break;
+    }
+    return need;
+}
+
 int validate_search(const knhip_index* idx, int64_t nq, int32_t k, int32_t& nprobe) {
     if (nq < 0 || k <= 0) {
         return fail(KNHIP_ERR_INVALID_ARGS, "nq must be >= 0 and k > 0");

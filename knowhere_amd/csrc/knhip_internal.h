@@ -323,11 +323,12 @@ struct knhip_index {
     mutable DevBuf rg_seg_dev;        // range_segments(): the segment table of the current lists, built on first use
     mutable int64_t rg_seg_nseg = -1, rg_seg_ncol = 0;
     mutable int64_t last_items_bound = 0;
+    bool prepared = false;            // knhip_index_prepare succeeded since the contents last changed (under mu)
 
     int64_t device_bytes() const {
         const DevBuf* all[] = {&centroids, &centroids_il, &centroids_bs, &cb, &precomp_t, &sq_trained, &d_list_len,
                                &d_list_row_off, &d_list_blk_off, &ids, &rows, &rows2, &d_list_blk_off2, &cb_t, &codes_aos,
-                               &rows_r, &d_list_blk_off_r, &psum, &rows_i, &idmap_ids, &idmap_col, &psum_s, &pqd_cb16, &pqd_st, &rows_bs, &bf_norm};
+                               &rows_r, &d_list_blk_off_r, &psum, &rows_i, &idmap_ids, &idmap_col, &psum_s, &pqd_cb16, &pqd_st, &rows_bs, &bf_norm, &xnorm};
         int64_t t = 0;
         for (auto* b : all) {
             t += (int64_t)b->bytes;
@@ -424,6 +425,20 @@ int ensure_pqf(const knhip_index* idx);
 int ensure_pqd(const knhip_index* idx);
 int ensure_pqi(const knhip_index* idx);
 int ensure_bf_split(const knhip_index* idx);
+// ---- knhip_index_prepare: the layouts above as a bit set, and what one batch of a search would build of them
+enum : unsigned {
+    KN_LAY_XNORM = 1,     // ensure_mscan_norms
+    KN_LAY_PSUM = 2,      // ensure_psum
+    KN_LAY_PQD = 4,       // ensure_pqd (+ psum)
+    KN_LAY_PQF = 8,       // ensure_pqf (+ psum)
+    KN_LAY_PQI = 16,      // ensure_pqi (+ pqf)
+    KN_LAY_SKEW = 32,     // build_pq_skew
+    KN_LAY_BF_SPLIT = 64, // ensure_bf_split
+    KN_LAY_IDMAP = 128    // the IVF-Flat direct map (knhip_index_get_vectors, knhip_index_calc_dist)
+};
+// (knhip_api_search.hip) the layouts search_batch(idx, nq, k, nprobe) may build on first use, whatever the guard of the IVF-PQ
+// prefilter decides: asked of plan_search, no HIP call.  Layouts that are ready are reported too
+unsigned search_batch_layouts(const knhip_index* idx, int64_t nq, int k, int nprobe, bool have_bitset);
 // what knhip_profile_get reports of the last search (under idx->mu): matrix-core BRUTE_FORCE, prefilter form, rank-0 phase, items
 void note_route(const knhip_index* idx, bool bf_mfma, int pq_form, bool rank0_phase, int64_t items_bound);
 // one batch of queries (device pointers), its coarse assignment [nq][nprobe] and where its results go

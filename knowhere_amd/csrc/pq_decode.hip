@@ -1272,6 +1272,20 @@ __global__ __launch_bounds__(PD_THREADS, 1) void pqd_kernel(MScanArgs a) {
 #endif
 }
 
+// the dynamic LDS size of the four forms of the filter kernel, for the current device: called where an index's decode layouts
+// are built (ensure_pqd), which every launch_pqd on that index follows -- not once per launch
+hipError_t pqd_prepare_launches() {
+    const void* kerns[4] = {reinterpret_cast<const void*>(pqd_kernel<true, true>), reinterpret_cast<const void*>(pqd_kernel<false, true>),
+                            reinterpret_cast<const void*>(pqd_kernel<true, false>), reinterpret_cast<const void*>(pqd_kernel<false, false>)};
+    for (const void* k : kerns) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PD_SMEM);
+        if (e != hipSuccess) {
+            return e;
+        }
+    }
+    return hipSuccess;
+}
+
 // filter pass only (no sample mode: pq_sample_kernel samples per query); the units must have been cut for PD_QT queries
 hipError_t launch_pqd(const MScanArgs& a, bool is_l2, int64_t units_bound, hipStream_t s) {
     if (units_bound <= 0) {
@@ -1289,13 +1303,9 @@ hipError_t launch_pqd(const MScanArgs& a, bool is_l2, int64_t units_bound, hipSt
     }
     auto kern = a.unit_loop ? (is_l2 ? pqd_kernel<true, true> : pqd_kernel<false, true>)
                             : (is_l2 ? pqd_kernel<true, false> : pqd_kernel<false, false>);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)PD_SMEM);
-    if (e != hipSuccess) {
-        return e;
-    }
+    // (the kernels' dynamic LDS size was raised by pqd_prepare_launches when the index's decode layouts were built)
     if (!a.unit_loop) {
-        e = hipMemsetAsync(a.pq_ctr, 0, 8 * 16 * sizeof(int32_t), s);
+        hipError_t e = hipMemsetAsync(a.pq_ctr, 0, 8 * 16 * sizeof(int32_t), s);
         if (e != hipSuccess) {
             return e;
         }

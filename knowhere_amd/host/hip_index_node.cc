@@ -40,6 +40,7 @@
 #include <cstdio>
 #include <atomic>
 #include <mutex>
+#include <map>
 #include <numeric>
 #include <shared_mutex>
 #include <thread>
@@ -420,6 +421,7 @@ class HipIndexNode : public IndexNode {
         std::vector<int32_t> devs;
         if (Status st = SelectDevices(c, /*deserialize=*/false, &devs); st != Status::success) return st;
         if (Status st = ReadRowType(c, devs); st != Status::success) return st;
+        if (Status st = ReadPrepare(c); st != Status::success) return st;
         if (Status st = CreateShards(devs); st != Status::success) return st;
         if constexpr (Kind == KNHIP_BRUTE_FORCE) {
             return Status::success;  // nothing to train
@@ -549,7 +551,7 @@ class HipIndexNode : public IndexNode {
                 if (Status st = AttachRawToGroup(); st != Status::success) return broken(st);
             }
         }
-        return Status::success;
+        return RunPrepare(/*check_fit=*/false);  // (a failure leaves the rows added and the index searchable)
     }
 
     expected<DataSetPtr>
@@ -1058,8 +1060,36 @@ class HipIndexNode : public IndexNode {
     // Accepts the blob of this node AND of the CPU node of the same kind (FLAT / IVF_FLAT / IVF_PQ / IVF_SQ8, or the
     // knowhere-1.x name "IVF", ivf.cc:1750-1757): same bytes.  Every length and cross-field relation is checked before a
     // pointer is handed to the C ABI: a corrupted BinarySet yields invalid_serialized_index_type, never a wild read.
+    // load (DeserializeLoad), then the prepare key: the layouts the named shapes would build lazily are built before the
+    // index is handed out.  Where the node chose the device itself (no gpu_id / gpu_ids: the one with the most free HBM),
+    // what prepare will add is first held against what that device has left -- an index that does not fit fails HERE,
+    // with the byte counts in the log, not in a later search
     Status
     Deserialize(const BinarySet& binset, std::shared_ptr<Config> cfg) override {
+        bool any = false, chosen_here = true;
+        std::vector<knhip_prepare_shape> shapes;
+        if (cfg) {
+            const auto& c = static_cast<const knowhere_config_type&>(*cfg);
+            if (c.prepare.has_value() && !HipParsePrepare(c.prepare.value(), &any, &shapes)) {
+                LOG_KNOWHERE_ERROR_ << TypeName() << ": prepare \"" << c.prepare.value() << "\": none, any or nq/k/nprobe,...";
+                return Status::invalid_args;
+            }
+            chosen_here = !c.gpu_id.has_value() && !c.gpu_ids.has_value();
+        }
+        if (Status st = DeserializeLoad(binset, cfg); st != Status::success) return st;
+        std::unique_lock<std::shared_mutex> lk(rw_);
+        prepare_any_ = any;
+        prepare_shapes_ = std::move(shapes);
+        const Status st = RunPrepare(chosen_here);
+        if (st != Status::success) {
+            DropShards();
+            row_scale_by_id_.clear();
+        }
+        return st;
+    }
+
+    Status
+    DeserializeLoad(const BinarySet& binset, std::shared_ptr<Config> cfg) {
         using namespace knhip_host;
         static const char* cpu_names[] = {"FLAT", "IVF_FLAT", "IVF_PQ", "IVF_SQ8"};
         BinaryPtr b = binset.GetByName(Type());
@@ -1462,6 +1492,58 @@ class HipIndexNode : public IndexNode {
         return Status::success;
     }
 
+    // the prepare key (hip_index_node.h) -> prepare_any_ / prepare_shapes_ (the config checked its syntax already)
+    Status
+    ReadPrepare(const knowhere_config_type& c) {
+        prepare_any_ = false;
+        prepare_shapes_.clear();
+        if (c.prepare.has_value() && !HipParsePrepare(c.prepare.value(), &prepare_any_, &prepare_shapes_)) {
+            LOG_KNOWHERE_ERROR_ << TypeName() << ": prepare \"" << c.prepare.value() << "\": none, any or nq/k/nprobe,...";
+            return Status::invalid_args;
+        }
+        return Status::success;
+    }
+
+    // knhip_index_prepare of every shard for the configured shapes (nothing configured: nothing happens).  check_fit: the
+    // dry-run figure of every device is first compared with the HBM the device has free
+    Status
+    RunPrepare(bool check_fit) {
+        if (!Built() || (!prepare_any_ && prepare_shapes_.empty())) return Status::success;
+        const knhip_prepare_shape* shapes = prepare_shapes_.empty() ? nullptr : prepare_shapes_.data();
+        const int32_t n = (int32_t)prepare_shapes_.size();
+        if (check_fit) {
+            std::map<int32_t, int64_t> want;  // per device: the shards that share one add up
+            for (const auto& s : sh_) {
+                int64_t extra = 0;
+                if (int rc = knhip_index_prepare_bytes(s.idx.p, shapes, n, &extra)) return ToStatus(rc);
+                want[s.device] += extra;
+            }
+            for (const auto& w : want) {
+                int64_t free_b = 0, total_b = 0;
+                if (knhip_device_memory(w.first, &free_b, &total_b) == KNHIP_OK && w.second > free_b) {
+                    LOG_KNOWHERE_ERROR_ << TypeName() << ": the index holds " << Size() << " bytes on the device(s); prepare needs "
+                                        << w.second << " more on device " << w.first << ", which has " << free_b << " of "
+                                        << total_b << " free: it does not fit";
+                    return Status::cuda_runtime_error;
+                }
+            }
+        }
+        int rc = KNHIP_OK;
+        const char* text = "";
+        if (group_.p) {
+            rc = knhip_shards_prepare(group_.p, shapes, n);
+            if (rc) text = knhip_shard_group_last_error();
+        } else {
+            rc = knhip_index_prepare(sh_[0].idx.p, shapes, n);
+            if (rc) text = knhip_last_error();
+        }
+        if (rc) {
+            LOG_KNOWHERE_ERROR_ << TypeName() << ": prepare: " << text;
+            return ToStatus(rc);
+        }
+        return Status::success;
+    }
+
     void
     DropShards() {
         group_.reset();
@@ -1708,6 +1790,9 @@ class HipIndexNode : public IndexNode {
     int64_t nbits_ = 8;  // IVF_PQ: code width (1 .. 8)
     int64_t sq_bits_ = 8;  // IVF_SQ8: code width of sq_type (SQ8 / SQ6 / SQ4)
     int32_t row_type_ = DefaultRowType;  // IVF_FLAT: KNHIP_ROWTYPE_* the device keeps the rows in (config key row_type)
+    // config key prepare: the layouts built at the end of every Add / Deserialize instead of by the first search that needs them
+    bool prepare_any_ = false;
+    std::vector<knhip_prepare_shape> prepare_shapes_;
     std::vector<Shard> sh_;        // one entry: the whole index on one device; several: list- (FLAT: row-) sharded
     GroupHandle group_;            // several shards: the exchange + merge host (include/knhip_shards.h)
     std::vector<int32_t> owner_;   // several shards, IVF kinds: list -> shard

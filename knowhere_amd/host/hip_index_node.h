@@ -69,10 +69,16 @@ HipCheckMetric(const BaseConfig& cfg, PARAM_TYPE param_type, std::string* err_ms
 //            the device (knhip_index_set_row_type).  Datasets, GetVectorByIds and the serialized blob stay fp32; rows that
 //            hold a value the type cannot represent exactly are refused (invalid_args), never rounded.  Every other index
 //            type refuses a value other than fp32, and so does an index sharded with gpu_ids.
+//   prepare  which of the layouts a first search would build lazily the node builds when the index is loaded
+//            (knhip_index_prepare): unset or "none" = none (a first search builds what it needs); "any" = what a search of
+//            any shape could need; otherwise a comma separated list of nq/k/nprobe, e.g. "10000/10/128,1/10/128".  Read at
+//            Train (it then holds for every Add of the index) and at Deserialize / DeserializeFromFile.  Anything else is
+//            invalid_args.
 #define KNHIP_DEVICE_CONFIG_MEMBERS \
     CFG_INT gpu_id;                 \
     CFG_STRING gpu_ids;             \
-    CFG_STRING row_type;
+    CFG_STRING row_type;            \
+    CFG_STRING prepare;
 #define KNHIP_DEVICE_CONFIG_FIELDS()                                                                        \
     KNOWHERE_CONFIG_DECLARE_FIELD(gpu_id)                                                                   \
         .description("device ordinal of the index (unset: round-robin / most free memory)")                \
@@ -89,6 +95,12 @@ HipCheckMetric(const BaseConfig& cfg, PARAM_TYPE param_type, std::string* err_ms
         .for_deserialize_from_file();                                                                       \
     KNOWHERE_CONFIG_DECLARE_FIELD(row_type)                                                                 \
         .description("GPU_HIP_IVF_FLAT: element type of the rows on the device: fp32, fp16 or bf16")        \
+        .allow_empty_without_default()                                                                      \
+        .for_train()                                                                                        \
+        .for_deserialize()                                                                                  \
+        .for_deserialize_from_file();                                                                       \
+    KNOWHERE_CONFIG_DECLARE_FIELD(prepare)                                                                  \
+        .description("layouts built at load instead of by the first search: none, any, or nq/k/nprobe,...") \
         .allow_empty_without_default()                                                                      \
         .for_train()                                                                                        \
         .for_deserialize()                                                                                  \
@@ -128,10 +140,60 @@ HipParseRowType(const std::string& s) {
     return t == "fp32" ? 0 : t == "fp16" ? 1 : t == "bf16" ? 2 : -1;
 }
 
-// the row_type key, in every config: a known name, and a narrow type on GPU_HIP_IVF_FLAT only
+// the prepare key: "none" (or empty) -> nothing, "any" -> *any, "nq/k/nprobe,..." -> shapes (uses = a search, no bitset);
+// false on anything else
+inline bool
+HipParsePrepare(const std::string& s, bool* any, std::vector<knhip_prepare_shape>* shapes) {
+    std::string t;
+    for (char c : s) {
+        if (!std::isspace((unsigned char)c)) t.push_back((char)std::tolower((unsigned char)c));
+    }
+    *any = false;
+    shapes->clear();
+    if (t.empty() || t == "none") return true;
+    if (t == "any") {
+        *any = true;
+        return true;
+    }
+    size_t pos = 0;
+    while (pos <= t.size()) {
+        const size_t e = t.find(',', pos);
+        const std::string shape = t.substr(pos, e == std::string::npos ? std::string::npos : e - pos);
+        int64_t v[3] = {0, 0, 0};
+        size_t p = 0;
+        for (int f = 0; f < 3; f++) {
+            const size_t q = f < 2 ? shape.find('/', p) : shape.size();
+            if (q == std::string::npos) return false;
+            const std::string tok = shape.substr(p, q - p);
+            if (tok.empty() || tok.size() > 9 || tok.find_first_not_of("0123456789") != std::string::npos) return false;
+            v[f] = std::atoll(tok.c_str());
+            p = q + 1;
+        }
+        if (v[0] < 1 || v[1] < 1 || v[1] > KNHIP_MAX_K || v[2] < 1) return false;
+        knhip_prepare_shape h{};
+        h.nq = v[0];
+        h.k = (int32_t)v[1];
+        h.nprobe = (int32_t)v[2];
+        h.uses = KNHIP_PREP_SEARCH;
+        shapes->push_back(h);
+        if (e == std::string::npos) break;
+        pos = e + 1;
+    }
+    return !shapes->empty();
+}
+
+// the row_type key, in every config: a known name, and a narrow type on GPU_HIP_IVF_FLAT only (and the prepare key: its syntax)
 template <typename Cfg>
 inline Status
 HipCheckRowType(const Cfg& cfg, bool ivf_flat, std::string* err_msg) {
+    if (cfg.prepare.has_value()) {
+        bool any = false;
+        std::vector<knhip_prepare_shape> shapes;
+        if (!HipParsePrepare(cfg.prepare.value(), &any, &shapes)) {
+            if (err_msg) *err_msg = "prepare \"" + cfg.prepare.value() + "\" is not none, any or a list of nq/k/nprobe";
+            return Status::invalid_args;
+        }
+    }
     if (!cfg.row_type.has_value()) return Status::success;
     const int32_t rt = HipParseRowType(cfg.row_type.value());
     if (rt < 0) {

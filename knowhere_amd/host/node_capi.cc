@@ -228,6 +228,8 @@ int knhip_node_calc_dist_by_ids(void* h, const float* q, int64_t nq, int64_t dim
 // where the index built / loaded last on the calling thread was placed (device ordinals in shard order): test hook
 int32_t knhip_node_last_placement(int32_t* out, int32_t cap) { return knhip_host_last_placement(out, cap); }
 
+// Index::Size: the HBM the index holds over all its devices (knhip_index_device_bytes of every shard + the refine stores)
+int64_t knhip_node_device_bytes(void* h) { return static_cast<Handle*>(h)->idx.Size(); }
 int64_t knhip_node_count(void* h) { return static_cast<Handle*>(h)->idx.Count(); }
 int64_t knhip_node_dim(void* h) { return static_cast<Handle*>(h)->idx.Dim(); }
 

@@ -796,6 +796,47 @@ int knhip_shard_group_calc_dist(knhip_shard_group* g, const float* queries, int6
     return rc == KNHIP_OK ? KNHIP_OK : fail(rc, err);
 }
 
+// knhip_index_prepare of every rank's index, each on a worker thread of its own (the ranks' layout kernels run side by side,
+// every index under its own mutex); the first failing rank's status and text are returned, the other ranks still finish
+int knhip_shards_prepare(knhip_shard_group* g, const knhip_prepare_shape* shapes, int32_t nshapes) {
+    if (!g) return fail(KNHIP_ERR_INVALID_ARGS, "shards_prepare: null group");
+    for (const Rank& r : g->ranks) {
+        if (!r.idx) return fail(KNHIP_ERR_INVALID_ARGS, "shards_prepare: a rank has no index");
+    }
+    std::lock_guard<std::mutex> call_lk(g->call_mu);
+    const int W = g->n;
+    std::vector<int> rcs((size_t)W, KNHIP_OK);
+    std::vector<std::string> errs((size_t)W);
+    std::vector<std::thread> th;
+    for (int r = 0; r < W; r++) {
+        th.emplace_back([&, r]() {
+            (void)hipSetDevice(g->ranks[r].dev);
+            rcs[(size_t)r] = knhip_index_prepare(const_cast<knhip_index*>(g->ranks[r].idx), shapes, nshapes);
+            if (rcs[(size_t)r] != KNHIP_OK) {
+                errs[(size_t)r] = std::string("rank ") + std::to_string(r) + ": " + knhip_last_error();
+            }
+        });
+    }
+    for (auto& t : th) t.join();
+    for (int r = 0; r < W; r++) {
+        if (rcs[(size_t)r] != KNHIP_OK) return fail(rcs[(size_t)r], errs[(size_t)r]);
+    }
+    return KNHIP_OK;
+}
+
+int knhip_shards_prepare_bytes(const knhip_shard_group* g, const knhip_prepare_shape* shapes, int32_t nshapes,
+                               int64_t* extra_bytes) {
+    if (!g || !extra_bytes) return fail(KNHIP_ERR_INVALID_ARGS, "shards_prepare_bytes: null group / output");
+    for (int r = 0; r < g->n; r++) {
+        extra_bytes[r] = 0;
+        if (!g->ranks[r].idx) return fail(KNHIP_ERR_INVALID_ARGS, "shards_prepare_bytes: a rank has no index");
+        if (int rc = knhip_index_prepare_bytes(g->ranks[r].idx, shapes, nshapes, &extra_bytes[r])) {
+            return fail(rc, std::string("rank ") + std::to_string(r) + ": " + knhip_last_error());
+        }
+    }
+    return KNHIP_OK;
+}
+
 const char* knhip_shard_group_last_error() { return g_err.c_str(); }
 
 }  // extern "C"

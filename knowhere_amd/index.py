@@ -13,6 +13,8 @@ from ._lib import KnhipError, check  # noqa: F401
 BRUTE_FORCE, IVF_FLAT, IVF_PQ, IVF_SQ8 = _lib.BRUTE_FORCE, _lib.IVF_FLAT, _lib.IVF_PQ, _lib.IVF_SQ8
 L2, IP = _lib.L2, _lib.IP
 ROWTYPE_FP32, ROWTYPE_FP16, ROWTYPE_BF16 = _lib.ROWTYPE_FP32, _lib.ROWTYPE_FP16, _lib.ROWTYPE_BF16
+PREP_SEARCH, PREP_RANGE, PREP_ITER, PREP_GET_VECTORS, PREP_CALC_DIST = (_lib.PREP_SEARCH, _lib.PREP_RANGE, _lib.PREP_ITER,
+                                                                        _lib.PREP_GET_VECTORS, _lib.PREP_CALC_DIST)
 
 KIND_NAMES = {"GPU_HIP_BRUTE_FORCE": BRUTE_FORCE, "GPU_HIP_IVF_FLAT": IVF_FLAT, "GPU_HIP_IVF_PQ": IVF_PQ,
               "GPU_HIP_IVF_SQ8": IVF_SQ8}
@@ -240,6 +242,39 @@ class GpuIndex:
     @property
     def uses_precomputed_table(self):
         return int(self.L.knhip_index_uses_precomputed_table(self.h))
+
+    # ---- prepare: the layouts a first search would build, up front (knhip_index_prepare) ----
+    @staticmethod
+    def _shapes(shapes):
+        """shapes: (nq, k, nprobe[, with_bitset[, uses]]) tuples or PrepareShape objects -> (ctypes array or None, count)"""
+        out = []
+        for s in shapes:
+            if not isinstance(s, _lib.PrepareShape):
+                s = tuple(s)
+                if not 3 <= len(s) <= 5:
+                    raise ValueError("a prepare shape is (nq, k, nprobe[, with_bitset[, uses]])")
+                s = _lib.PrepareShape(int(s[0]), int(s[1]), int(s[2]), int(s[3]) if len(s) > 3 else 0,
+                                      int(s[4]) if len(s) > 4 else PREP_SEARCH)
+            out.append(s)
+        return ((_lib.PrepareShape * len(out))(*out) if out else None), len(out)
+
+    def prepare(self, shapes=()):
+        """build every layout a first search of these shapes would build lazily; () = a search of any shape and every use.
+        Cumulative and idempotent; a layout that does not fit raises KnhipError naming it, the index stays searchable"""
+        arr, n = self._shapes(shapes)
+        check(self.L.knhip_index_prepare(self.h, arr, n))
+
+    def prepare_bytes(self, shapes=()):
+        """the bytes device_bytes would grow by under prepare(shapes): exact, nothing is allocated"""
+        arr, n = self._shapes(shapes)
+        out = C.c_int64(0)
+        check(self.L.knhip_index_prepare_bytes(self.h, arr, n, C.byref(out)))
+        return int(out.value)
+
+    @property
+    def prepared(self):
+        """1 after a successful prepare, 0 again after the next Add"""
+        return int(self.L.knhip_index_prepared(self.h))
 
     # ---- search ----
     def search(self, xq, k, nprobe=1, bitset=None, nbits=0):

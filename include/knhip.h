@@ -36,6 +36,11 @@
  *                                        IndexIVFFlat::calc_dist_by_ids (thirdparty/faiss/faiss/cppcontrib/knowhere/
  *                                        IndexIVFFlat.cpp:665-763): the rerank primitive of the embedding-list strategies
  *                                        (RerankByCalcDistByStorageIds, src/index/emb_list/emb_list_strategy.cc:45-117)
+ *   knhip_index_maxsim*                  that rerank loop itself for the MAX_SIM* metrics: one CalcDistByStorageIds per candidate
+ *                                        document + get_sum_max_sim (include/knowhere/emb_list_utils.h:123-176), fused: the
+ *                                        scores of all candidate documents of all query lists in one enqueue
+ *   knhip_emb_list_search                TokenANNEmbListStrategy::Search (src/index/emb_list/emb_list_strategy_token_ann.cc:
+ *                                        51-175) behind IndexNode::SearchEmbList (src/index/index_node.cc:252-297)
  *
  * Numeric contract ("exact" mode, the default): every distance is computed with the
  * reference's scalar operation order, one IEEE rounding per operation (no FMA contraction),
@@ -80,6 +85,7 @@ extern "C" {
  * Additive since 9: knhip_index_set_row_type / knhip_index_get_row_type (IVF_FLAT rows kept as fp16 / bf16 in HBM).
  * Additive since 9: knhip_index_calc_dist / knhip_index_calc_dist_device (CalcDistByIDs: exact distances to given ids).
  * Additive since 9: knhip_index_prepare / knhip_index_prepare_bytes / knhip_index_prepared (the lazily built layouts, up front).
+ * Additive since 9: knhip_index_maxsim / knhip_index_maxsim_device / knhip_emb_list_search (embedding lists: MAX_SIM rerank, TokenANN).
  * Callers compare knhip_abi_version() with the header they were built against. */
 #define KNHIP_ABI_VERSION 9
 /* Largest k of a search and largest k_base of a refine (additive since 9: the large-k path, knhip_select_ordered_device). */
@@ -484,6 +490,47 @@ int knhip_index_calc_dist(const knhip_index* idx, const float* queries, int64_t 
                           const int64_t* labels, float* out_dist);
 int knhip_index_calc_dist_device(const knhip_index* idx, const float* d_queries, int64_t nq, int64_t n_labels,
                                  const int64_t* d_labels, float* d_out_dist, int64_t* d_nabsent, void* stream);
+
+/* ---- embedding lists: documents of several vectors, scored by MaxSim (the reference's MAX_SIM* metrics) ----
+ * Score of a document with rows y_0 .. y_{m-1} against a query list q_0 .. q_{n-1}, dist(i, j) being the 32 bits
+ * knhip_index_calc_dist returns for the pair: m_i = -FLT_MAX, for every j `if (dist > m_i) m_i = dist` (L2 index: +FLT_MAX
+ * and `<`), then score = 0.0f and score += m_i for i ASCENDING, one fp32 rounding per add (find_max_in_range /
+ * find_min_in_range / get_sum_max_sim of the reference).  The compare is strict: a NaN or -inf (L2: +inf) distance is never
+ * taken, m_i then stays at -/+FLT_MAX.  A list without a query scores 0.0f.
+ * scores of candidate documents: nel query lists; list e = queries rows q_lims[e] .. q_lims[e+1]-1 and candidate
+ * documents cand_lims[e] .. cand_lims[e+1]-1; document c = labels[doc_lims[c] .. doc_lims[c+1]-1]; out_scores[c].
+ * Every limit array ascends; labels may repeat inside a document and across documents and lists.  The nq x L distance
+ * matrix is never written: one fused gather + contraction + segmented extremum per list, all lists enqueued without a
+ * host synchronisation between them.  Scratch: 4 bytes per (candidate document, query of its list), in rounds of at most
+ * KNHIP_MAXSIM_ROUND_KB (default 256 MiB) when a call needs more.
+ * Kinds and refusals as knhip_index_calc_dist: BRUTE_FORCE and IVF_FLAT, KNHIP_ERR_NOT_IMPLEMENTED for IVF_PQ / IVF_SQ8,
+ * arguments checked before any device is touched; nel == 0 or no candidate document: KNHIP_OK, nothing touched.
+ * Host form, strict: a document without a label is KNHIP_ERR_INVALID_ARGS; a label that is not stored is
+ * KNHIP_ERR_INVALID_ARGS, knhip_last_error names the label and its position in `labels`, out_scores is left unwritten.
+ * Device form, tolerant: d_doc_lims / d_labels (n_labels entries) / d_out_scores are device arrays, the two per-list limit
+ * arrays stay on the host; the score of a document with an absent label is the all-ones pattern and *d_nabsent (if not
+ * NULL; a device int64) receives the number of absent labels; a document without a label is not scored by the reference
+ * and gets n times -/+FLT_MAX here.  Enqueued on `stream`, not synchronised.  The first call after an Add on an IVF_FLAT
+ * index builds the direct map, as CalcDistByIDs does: KNHIP_PREP_CALC_DIST of knhip_index_prepare covers that layout. */
+int knhip_index_maxsim(const knhip_index* idx, const float* queries, const int64_t* q_lims, int64_t nel,
+                       const int64_t* cand_lims, const int64_t* doc_lims, const int64_t* labels, float* out_scores);
+int knhip_index_maxsim_device(const knhip_index* idx, const float* d_queries, const int64_t* q_lims /*host*/, int64_t nel,
+                              const int64_t* cand_lims /*host*/, const int64_t* d_doc_lims, const int64_t* d_labels,
+                              int64_t n_labels, float* d_out_scores, int64_t* d_nabsent, void* stream);
+/* TokenANN search: document e of the index = storage ids doc_offsets[e] .. doc_offsets[e+1]-1 (ndocs + 1 ascending entries).
+ * Stage 1: ONE knhip_search of all the lists' query vectors with k = vec_topk (1 <= vec_topk <= KNHIP_MAX_K; the same search,
+ * tie rule included; bitset over storage ids), the queries uploaded once.  Per list, the documents of its result ids
+ * (document of id v = upper_bound(doc_offsets, v) - 1; one >= ndocs is KNHIP_ERR_INVALID_ARGS, the reference's "invalid
+ * emb_list id"; empty documents skipped) are its candidates; one maxsim enqueue scores the candidates of all lists.
+ * Selection of k per list: candidates pass a heap in ARRIVAL order, admission needs a strict improvement over the worst
+ * kept entry, eviction removes the worst by (score, id); output best first -- IP / COSINE (score desc, id desc), L2 (score
+ * asc, id asc) --, missing slots id -1 and score -FLT_MAX (L2: +FLT_MAX).  Which of several documents tied AT the k-th score
+ * survives depends on the arrival order; the reference's is the iteration order of a std::unordered_set<size_t> filled from
+ * the stage-1 ids in row-major order, negative ids skipped.  The same container is filled in the same sequence here, which
+ * matches the boundary choice for a reference built with the same standard library.  Outputs [nel][k]. */
+int knhip_emb_list_search(const knhip_index* idx, const int64_t* doc_offsets, int64_t ndocs, const float* queries,
+                          const int64_t* q_lims, int64_t nel, int32_t k, int32_t vec_topk, int32_t nprobe,
+                          const uint8_t* bitset, int64_t bitset_nbits, int64_t* out_doc_ids, float* out_scores);
 /* Same with every buffer already in HBM; enqueued on `stream` (hipStream_t, NULL = default
  * stream) and NOT synchronised at the end.  One exception inside: an IVF_PQ m = 32 batch that takes the matrix-core
  * prefilter (pq_filter.hip) waits once on `stream` in the middle of the batch the FIRST time a (k, nprobe) pair is seen

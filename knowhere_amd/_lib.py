@@ -66,6 +66,7 @@ SYMBOLS = [
     "knhip_select_ordered_device", "knhip_index_calc_dist", "knhip_index_calc_dist_device",
     "knhip_iter_create", "knhip_iter_next", "knhip_iter_next_all", "knhip_iter_has_next", "knhip_iter_stats", "knhip_iter_destroy",
     "knhip_index_prepare", "knhip_index_prepare_bytes", "knhip_index_prepared",
+    "knhip_index_maxsim", "knhip_index_maxsim_device", "knhip_emb_list_search",
 ]
 
 # `uses` of a PrepareShape (KNHIP_PREP_* of include/knhip.h): what the index is prepared for
@@ -208,6 +209,9 @@ def load():
     L.knhip_index_find_vectors.argtypes = [vp, i64, vp, vp, vp]
     L.knhip_index_calc_dist.argtypes = [vp, vp, i64, i64, vp, vp]
     L.knhip_index_calc_dist_device.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp]
+    L.knhip_index_maxsim.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
+    L.knhip_index_maxsim_device.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp]
+    L.knhip_emb_list_search.argtypes = [vp, vp, i64, vp, vp, i64, i32, i32, i32, vp, i64, vp, vp]
     L.knhip_index_assign.argtypes = [vp, i64, vp, vp]
     L.knhip_device_memory.argtypes = [i32, vp, vp]
     L.knhip_rows_create.argtypes = [i32, i32, i32, C.POINTER(vp)]

@@ -196,18 +196,7 @@ __global__ __launch_bounds__(256) void coarse_gemm_kernel(const float* __restric
 //   pass 2: every centroid with approx <= B_q is appended to the query's candidate list (~1.2 ncand of them).
 // Everything unselected has approx > B_q: B_q is the certificate's T.  M = centroids, N = queries (A = centroids).
 // order-preserving float <-> uint32 keys ("better" = smaller key): used by the bound selection above the re-rank kernel's own
-template <bool IS_L2>
-__device__ __forceinline__ uint32_t cr_key_fwd(float f) {
-    const uint32_t b = __float_as_uint(f);
-    const uint32_t asc = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return IS_L2 ? asc : ~asc;
-}
-template <bool IS_L2>
-__device__ __forceinline__ float cr_unkey_fwd(uint32_t key) {
-    const uint32_t asc = IS_L2 ? key : ~key;
-    const uint32_t b = (asc & 0x80000000u) ? (asc & 0x7fffffffu) : ~asc;
-    return __uint_as_float(b);
-}
+// (cr_key_fwd / cr_unkey_fwd: common.h)
 
 typedef __bf16 cg_bf8 __attribute__((ext_vector_type(8)));
 typedef __bf16 cg_bf4 __attribute__((ext_vector_type(4)));

@@ -95,6 +95,21 @@ __device__ __forceinline__ float worst_dist() {
     return IS_L2 ? FLT_MAX : -FLT_MAX;
 }
 
+// order-preserving float <-> uint32 keys ("better" = smaller key): the coarse stage's bound selection (coarse_gemm.hip) and the
+// MaxSim extrema (refine.hip) combine values as integers through them
+template <bool IS_L2>
+__device__ __forceinline__ uint32_t cr_key_fwd(float f) {
+    const uint32_t b = __float_as_uint(f);
+    const uint32_t asc = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return IS_L2 ? asc : ~asc;
+}
+template <bool IS_L2>
+__device__ __forceinline__ float cr_unkey_fwd(uint32_t key) {
+    const uint32_t asc = IS_L2 ? key : ~key;
+    const uint32_t b = (asc & 0x80000000u) ? (asc & 0x7fffffffu) : ~asc;
+    return __uint_as_float(b);
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (KN_WAVE - 1); }
 
 // 64-bit shuffle helpers (ds_bpermute based; used only on slow paths)

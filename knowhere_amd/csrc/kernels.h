@@ -738,6 +738,21 @@ struct CalcDistArgs {
 hipError_t launch_calc_dist(const CalcDistArgs& a, bool is_l2, int row_type, hipStream_t s,
                             int64_t round_labels = (int64_t)1 << 22, int64_t round_queries = (int64_t)1 << 19);
 
+// MaxSim (refine.hip, maxsim_score_kernel): the scores of the candidate documents c_lo .. c_hi - 1 of ONE query list.
+// Document c = labels[doc_lims[c] .. doc_lims[c + 1]); out_scores[c] = sum over the list's queries, in order, of the best
+// distance to a row of the document (the all-ones pattern when a label of the document is not stored here).
+struct MaxSimArgs {
+    CalcDistArgs cd;          // the store and the list: queries / nq = the list's own; labels / nlabels = the call's whole label
+                              // array; nabsent / first_absent as CalcDistByIDs (positions in that array); out* unused
+    const int64_t* doc_lims;  // device; entries c_lo .. c_hi are read
+    int64_t c_lo, c_hi;
+    uint32_t* ext;            // scratch [(c_hi - c_lo)][nq] order-preserving keys of the extrema
+    float* out_scores;        // indexed by c
+};
+// three launches on s: init (ext, out_scores[c_lo .. c_hi)), score, sum.  ntiles: label tiles of CD_ROWS to cover, at least
+// (doc_lims[c_hi] - doc_lims[c_lo]) / CD_ROWS rounded up (workgroups behind the last label leave at once)
+hipError_t launch_maxsim(const MaxSimArgs& m, bool is_l2, int row_type, int64_t ntiles, hipStream_t s);
+
 // ---- build.hip: Train / Add on the device ----
 // direct map of an IVF-Flat index (GetVectorByIds): ids sorted with the columns of their rows in the interleaved store
 size_t idmap_sort_tmp_bytes(int64_t n);

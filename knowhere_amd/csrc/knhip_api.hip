@@ -3,6 +3,11 @@
 // of this directory is knhip_api_search.hip.
 #include "knhip_internal.h"
 
+#include <functional>
+#include <queue>
+#include <type_traits>
+#include <unordered_set>
+
 namespace knhip_host {
 
 thread_local std::string g_last_error;
@@ -1773,6 +1778,376 @@ int knhip_index_calc_dist(const knhip_index* idx, const float* queries, int64_t 
     }
     HIP_TRY(hipMemcpy(out_dist, dout.p, (size_t)nq * (size_t)n_labels * sizeof(float), hipMemcpyDeviceToHost));
     return KNHIP_OK;
+}
+
+// ---- MaxSim over candidate documents (the MAX_SIM* rerank of the embedding-list strategies, reference
+// src/index/emb_list/emb_list_strategy.cc:45-117 + include/knowhere/emb_list_utils.h:123-176): refine.hip, maxsim_score_kernel ---
+// what both forms check without touching a device; *ncand = candidate documents of the call, 0: nothing to do
+static int maxsim_check(const knhip_index* idx, const char* who, const void* q, const int64_t* q_lims, int64_t nel,
+                        const int64_t* cand_lims, const void* doc_lims, const void* labels, const void* out, int64_t* ncand) {
+    if (int rc = check_index(idx)) return rc;
+    const int kind = idx->desc.kind;
+    if (kind != KNHIP_BRUTE_FORCE && kind != KNHIP_IVF_FLAT) {
+        return fail(KNHIP_ERR_NOT_IMPLEMENTED, std::string(who) + ": only BRUTE_FORCE and IVF_FLAT keep the rows (the reference: "
+                                                                  "only support IndexIVFFlat and IndexIVFFlatCC)");
+    }
+    *ncand = 0;
+    if (nel < 0) {
+        return fail(KNHIP_ERR_INVALID_ARGS, std::string(who) + ": negative count");
+    }
+    if (nel == 0) {
+        return KNHIP_OK;
+    }
+    if (!q_lims || !cand_lims) {
+        return fail(KNHIP_ERR_INVALID_ARGS, std::string(who) + ": null q_lims / cand_lims");
+    }
+    if (q_lims[0] < 0 || cand_lims[0] < 0) {
+        return fail(KNHIP_ERR_INVALID_ARGS, std::string(who) + ": negative limit");
+    }
+    for (int64_t e = 0; e < nel; e++) {
+        if (q_lims[e + 1] < q_lims[e] || cand_lims[e + 1] < cand_lims[e]) {
+            return fail(KNHIP_ERR_INVALID_ARGS, std::string(who) + ": q_lims and cand_lims must ascend (list " + std::to_string(e) + ")");
+        }
+        if (q_lims[e + 1] - q_lims[e] > (int64_t)65535 * CD_QT) {
+            return fail(KNHIP_ERR_INVALID_ARGS, std::string(who) + ": more than 2097120 query vectors in list " + std::to_string(e));
+        }
+    }
+    *ncand = cand_lims[nel] - cand_lims[0];
+    if (*ncand > 0 && (!doc_lims || !labels || !out || (q_lims[nel] > q_lims[0] && !q))) {
+        return fail(KNHIP_ERR_INVALID_ARGS, std::string(who) + ": null query / doc_lims / label / output pointer");
+    }
+    return KNHIP_OK;
+}
+
+// Enqueues the scores of every list's candidates on s: per list (and per round of it) init + score + sum, nothing waits for
+// the host in between.  ext holds the extrema keys: the lists' pieces are packed one behind the other, and when the cap is
+// reached the packing starts again at the front -- stream order has the earlier piece summed by then (a "round").
+// h_doc_lims (may be null): the host's copy of d_doc_lims -- the score grid then covers exactly a piece's labels.
+static int maxsim_enqueue(const knhip_index* idx, DevBuf& ext, const float* d_q, const int64_t* q_lims, int64_t nel,
+                          const int64_t* cand_lims, const int64_t* d_doc_lims, const int64_t* h_doc_lims,
+                          const int64_t* d_labels, int64_t n_labels, float* d_out, unsigned long long* nabsent,
+                          unsigned long long* first_absent, hipStream_t s) {
+    MaxSimArgs m{};
+    CalcDistArgs& a = m.cd;
+    if (idx->desc.kind == KNHIP_IVF_FLAT) {
+        if (int rc = ensure_idmap(idx)) return rc;
+        a.rows = idx->rows.p;
+        a.idmap_ids = idx->idmap_ids.as<int64_t>();
+        a.idmap_col = idx->idmap_col.as<int64_t>();
+        a.ntotal = a.idmap_ids ? idx->ntotal : 0;
+    } else {
+        a.aos = (idx->d & 3) == 0 && idx->codes_aos.p != nullptr; // (as CalcDistByIDs: calc_dist_enqueue)
+        a.rows = a.aos ? idx->codes_aos.p : idx->rows.p;
+        a.ntotal = a.rows ? idx->ntotal : 0;
+        a.id_offset = idx->id_offset;
+    }
+    const int rt = idx->desc.kind == KNHIP_IVF_FLAT ? idx->row_type : KN_ROW_FP32;
+    a.d = idx->d;
+    a.nchunk = row_nchunk(idx->d, rt);
+    a.labels = d_labels;
+    a.nlabels = n_labels;
+    a.row_scale = idx->row_scale.as<float>();
+    a.cos_mode = idx->is_l2 ? 0 : idx->cos_mode;
+    a.nabsent = nabsent;
+    a.first_absent = first_absent;
+    m.doc_lims = d_doc_lims;
+    m.out_scores = d_out;
+    // the scratch: everything the call needs, or the cap (at least one document of the longest list)
+    size_t total = 0, one = 0;
+    for (int64_t e = 0; e < nel; e++) {
+        const size_t n = (size_t)(q_lims[e + 1] - q_lims[e]);
+        total += (size_t)(cand_lims[e + 1] - cand_lims[e]) * n * sizeof(uint32_t);
+        one = std::max(one, n * sizeof(uint32_t));
+    }
+    const size_t cap = std::max(std::min(total, env_search().maxsim_round_bytes), one);
+    HIP_TRY(ext.reserve(cap));
+    size_t off = 0;
+    for (int64_t e = 0; e < nel; e++) {
+        const int64_t n = q_lims[e + 1] - q_lims[e];
+        a.queries = d_q ? d_q + q_lims[e] * idx->d : nullptr;
+        a.nq = n;
+        const size_t per = (size_t)n * sizeof(uint32_t);
+        for (int64_t c = cand_lims[e]; c < cand_lims[e + 1];) {
+            int64_t take = std::min<int64_t>(cand_lims[e + 1] - c, ((int64_t)1 << 30) - 1);
+            if (per > 0) {
+                if ((cap - off) / per == 0) {
+                    off = 0; // the next round
+                }
+                take = std::min<int64_t>(take, (int64_t)((cap - off) / per));
+            }
+            m.c_lo = c;
+            m.c_hi = c + take;
+            m.ext = reinterpret_cast<uint32_t*>(static_cast<char*>(ext.p) + off);
+            const int64_t nl = h_doc_lims ? h_doc_lims[c + take] - h_doc_lims[c] : n_labels;
+            HIP_TRY(launch_maxsim(m, idx->is_l2, rt, (nl + CD_ROWS - 1) / CD_ROWS, s));
+            off += (size_t)take * per;
+            c += take;
+        }
+    }
+    return KNHIP_OK;
+}
+
+int knhip_index_maxsim_device(const knhip_index* idx, const float* d_queries, const int64_t* q_lims, int64_t nel,
+                              const int64_t* cand_lims, const int64_t* d_doc_lims, const int64_t* d_labels, int64_t n_labels,
+                              float* d_out_scores, int64_t* d_nabsent, void* stream) {
+    int64_t ncand = 0;
+    if (int rc = maxsim_check(idx, "maxsim_device", d_queries, q_lims, nel, cand_lims, d_doc_lims, d_labels, d_out_scores, &ncand)) {
+        return rc;
+    }
+    if (n_labels < 0) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "maxsim_device: negative count");
+    }
+    if (ncand == 0) {
+        return KNHIP_OK;
+    }
+    DeviceGuard g(idx->desc.device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Workspace* ws = acquire_ws(idx, stream, true);
+    std::lock_guard<std::mutex> ws_lock(ws->mu); // two host threads enqueueing on one stream share this scratch
+    if (d_nabsent) {
+        HIP_TRY(hipMemsetAsync(d_nabsent, 0, sizeof(int64_t), s));
+    }
+    return maxsim_enqueue(idx, ws->mx_ext, d_queries, q_lims, nel, cand_lims, d_doc_lims, nullptr, d_labels, n_labels, d_out_scores,
+                          reinterpret_cast<unsigned long long*>(d_nabsent), nullptr, s);
+}
+
+// the host forms' shared tail: limits and labels up, the enqueue, the absent words and the scores [c0, c1) down.
+// d_q: the queries, already on the device (row 0 = the row q_lims counts from)
+static int maxsim_host_run(const knhip_index* idx, Workspace* ws, const float* d_q, const int64_t* q_lims, int64_t nel,
+                           const int64_t* cand_lims, const int64_t* doc_lims, const int64_t* labels, float* out_scores,
+                           hipStream_t s) {
+    const int64_t c0 = cand_lims[0], c1 = cand_lims[nel];
+    const int64_t n_labels = doc_lims[c1];
+    HIP_TRY(ws->mx_lims.reserve((size_t)(c1 + 1) * sizeof(int64_t)));
+    HIP_TRY(ws->mx_labels.reserve((size_t)n_labels * sizeof(int64_t)));
+    HIP_TRY(ws->mx_scores.reserve((size_t)c1 * sizeof(float)));
+    HIP_TRY(ws->mx_abs.reserve(2 * sizeof(unsigned long long)));
+    const unsigned long long init[2] = {0ull, ~0ull};
+    HIP_TRY(hipMemcpyAsync(ws->mx_lims.p, doc_lims, (size_t)(c1 + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ws->mx_labels.p, labels, (size_t)n_labels * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ws->mx_abs.p, init, sizeof(init), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s)); // (`init` lives on this frame; nothing of the scoring is enqueued yet)
+    if (int rc = maxsim_enqueue(idx, ws->mx_ext, d_q, q_lims, nel, cand_lims, ws->mx_lims.as<int64_t>(), doc_lims,
+                                ws->mx_labels.as<int64_t>(), n_labels, ws->mx_scores.as<float>(),
+                                ws->mx_abs.as<unsigned long long>(), ws->mx_abs.as<unsigned long long>() + 1, s)) {
+        return rc;
+    }
+    unsigned long long absent[2] = {0ull, 0ull};
+    HIP_TRY(hipMemcpyAsync(absent, ws->mx_abs.p, sizeof(absent), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s)); // (the one wait for the kernels)
+    if (absent[0] != 0ull) {
+        const int64_t pos = (int64_t)absent[1];
+        return fail(KNHIP_ERR_INVALID_ARGS, "maxsim: label " + std::to_string(labels[pos]) + " at position " + std::to_string(pos) +
+                                                    " is not in the index (" + std::to_string(absent[0]) + " absent)");
+    }
+    HIP_TRY(hipMemcpy(out_scores + c0, ws->mx_scores.as<float>() + c0, (size_t)(c1 - c0) * sizeof(float), hipMemcpyDeviceToHost));
+    return KNHIP_OK;
+}
+
+// documents of the host forms: every one holds a label, the limits ascend
+static int maxsim_check_docs(const char* who, const int64_t* doc_lims, int64_t c0, int64_t c1) {
+    if (doc_lims[c0] < 0) {
+        return fail(KNHIP_ERR_INVALID_ARGS, std::string(who) + ": negative limit");
+    }
+    for (int64_t c = c0; c < c1; c++) {
+        if (doc_lims[c + 1] <= doc_lims[c]) {
+            return fail(KNHIP_ERR_INVALID_ARGS, std::string(who) + ": document " + std::to_string(c) + " holds no label (the reference "
+                                                                   "skips empty documents before they are scored)");
+        }
+    }
+    return KNHIP_OK;
+}
+
+int knhip_index_maxsim(const knhip_index* idx, const float* queries, const int64_t* q_lims, int64_t nel, const int64_t* cand_lims,
+                       const int64_t* doc_lims, const int64_t* labels, float* out_scores) {
+    int64_t ncand = 0;
+    if (int rc = maxsim_check(idx, "maxsim", queries, q_lims, nel, cand_lims, doc_lims, labels, out_scores, &ncand)) return rc;
+    if (ncand == 0) {
+        return KNHIP_OK;
+    }
+    if (int rc = maxsim_check_docs("maxsim", doc_lims, cand_lims[0], cand_lims[nel])) return rc;
+    DeviceGuard g(idx->desc.device);
+    hipStream_t s = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    Workspace* ws = acquire_ws(idx, nullptr, false);
+    auto run = [&]() -> int {
+        const size_t qbytes = (size_t)q_lims[nel] * idx->d * sizeof(float);
+        HIP_TRY(ws->h_queries.reserve(qbytes));
+        if (qbytes) {
+            HIP_TRY(hipMemcpyAsync(ws->h_queries.p, queries, qbytes, hipMemcpyHostToDevice, s));
+        }
+        return maxsim_host_run(idx, ws, ws->h_queries.as<float>(), q_lims, nel, cand_lims, doc_lims, labels, out_scores, s);
+    };
+    const int rc = run();
+    if (rc != KNHIP_OK) {
+        (void)hipStreamSynchronize(s);
+    }
+    release_ws(idx, ws);
+    (void)hipStreamDestroy(s);
+    return rc;
+}
+
+// ---- TokenANN (reference src/index/emb_list/emb_list_strategy_token_ann.cc:51-175): stage 1 = one search of every query vector,
+// stage 2 = MaxSim of each list against the documents its vectors' neighbours belong to, the k best documents per list --------
+} // extern "C"
+
+namespace {
+struct DocScore { // IdVal<int64_t, float> of the reference (include/knowhere/object.h:25-50): ordered by (val, id)
+    int64_t id;
+    float val;
+    bool operator<(const DocScore& o) const { return val < o.val || (val == o.val && id < o.id); }
+    bool operator>(const DocScore& o) const { return !(*this < o) && !(id == o.id && val == o.val); }
+};
+// RerankByCalcDistByStorageIds' heap over the candidates in arrival order; out best first, then id -1 / the neutral score
+template <bool LARGER>
+void select_docs(const int64_t* docs, const float* scores, int64_t n, int32_t k, int64_t* out_ids, float* out_scores) {
+    using Cmp = std::conditional_t<LARGER, std::greater<DocScore>, std::less<DocScore>>;
+    std::priority_queue<DocScore, std::vector<DocScore>, Cmp> heap;
+    for (int64_t i = 0; i < n; i++) {
+        if (heap.size() < (size_t)k) {
+            heap.push(DocScore{docs[i], scores[i]});
+        } else if (LARGER ? scores[i] > heap.top().val : scores[i] < heap.top().val) {
+            heap.pop();
+            heap.push(DocScore{docs[i], scores[i]});
+        }
+    }
+    const size_t got = heap.size();
+    for (size_t j = 0; j < got; j++) {
+        out_ids[got - j - 1] = heap.top().id;
+        out_scores[got - j - 1] = heap.top().val;
+        heap.pop();
+    }
+    std::fill(out_ids + got, out_ids + k, (int64_t)-1);
+    std::fill(out_scores + got, out_scores + k, LARGER ? -FLT_MAX : FLT_MAX);
+}
+} // namespace
+
+extern "C" {
+
+int knhip_emb_list_search(const knhip_index* idx, const int64_t* doc_offsets, int64_t ndocs, const float* queries,
+                          const int64_t* q_lims, int64_t nel, int32_t k, int32_t vec_topk, int32_t nprobe, const uint8_t* bitset,
+                          int64_t bitset_nbits, int64_t* out_doc_ids, float* out_scores) {
+    if (int rc = check_index(idx)) return rc;
+    const int kind = idx->desc.kind;
+    if (kind != KNHIP_BRUTE_FORCE && kind != KNHIP_IVF_FLAT) {
+        return fail(KNHIP_ERR_NOT_IMPLEMENTED, "emb_list_search: only BRUTE_FORCE and IVF_FLAT keep the rows the rerank reads");
+    }
+    if (nel < 0 || ndocs < 0 || k <= 0 || vec_topk < 1 || vec_topk > KNHIP_MAX_K) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "emb_list_search: nel >= 0, ndocs >= 0, k > 0 and 1 <= vec_topk <= 16384 required");
+    }
+    if (nel == 0) {
+        return KNHIP_OK;
+    }
+    if (!doc_offsets || !q_lims || !out_doc_ids || !out_scores) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "emb_list_search: null doc_offsets / q_lims / output pointer");
+    }
+    if (q_lims[0] != 0) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "emb_list_search: q_lims[0] must be 0");
+    }
+    for (int64_t e = 0; e < nel; e++) {
+        if (q_lims[e + 1] < q_lims[e] || q_lims[e + 1] - q_lims[e] > (int64_t)65535 * CD_QT) {
+            return fail(KNHIP_ERR_INVALID_ARGS, "emb_list_search: q_lims must ascend, at most 2097120 vectors per list");
+        }
+    }
+    for (int64_t e = 0; e < ndocs; e++) {
+        if (doc_offsets[e + 1] < doc_offsets[e]) {
+            return fail(KNHIP_ERR_INVALID_ARGS, "emb_list_search: doc_offsets must ascend");
+        }
+    }
+    const int64_t nq = q_lims[nel];
+    if (nq > 0 && !queries) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "emb_list_search: null query pointer");
+    }
+    if (int rc = validate_search(idx, nq, vec_topk, nprobe)) return rc;
+    DeviceGuard g(idx->desc.device);
+    hipStream_t s = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    Workspace* ws = acquire_ws(idx, nullptr, false);
+    auto run = [&]() -> int {
+        std::vector<int64_t> ids((size_t)nq * vec_topk);
+        if (nq > 0) {
+            // ---- stage 1: search_host_impl's body, the queries staying in the workspace for stage 2
+            const size_t qbytes = (size_t)nq * idx->d * sizeof(float);
+            HIP_TRY(ws->h_queries.reserve(qbytes));
+            HIP_TRY(ws->h_out_d.reserve((size_t)nq * vec_topk * sizeof(float)));
+            HIP_TRY(ws->h_out_i.reserve((size_t)nq * vec_topk * sizeof(int64_t)));
+            HIP_TRY(hipMemcpyAsync(ws->h_queries.p, queries, qbytes, hipMemcpyHostToDevice, s));
+            const uint8_t* d_bitset = nullptr;
+            if (bitset && bitset_nbits > 0) {
+                const size_t bb = (size_t)((bitset_nbits + 7) / 8);
+                HIP_TRY(ws->h_bitset.reserve(bb));
+                HIP_TRY(hipMemcpyAsync(ws->h_bitset.p, bitset, bb, hipMemcpyHostToDevice, s));
+                d_bitset = ws->h_bitset.as<uint8_t>();
+            }
+            const int64_t qb = query_batch(idx, nq, vec_topk, nprobe);
+            if (idx->desc.kind != KNHIP_BRUTE_FORCE) {
+                std::lock_guard<std::mutex> lk(idx->mu);
+                idx->coarse_flops += 2.0 * (double)nq * (double)idx->nlist * (double)idx->d;
+            }
+            for (int64_t q0 = 0; q0 < nq; q0 += qb) {
+                const int64_t n = std::min(qb, nq - q0);
+                if (int r = search_batch_ties(idx, ws, ws->h_queries.as<float>() + q0 * idx->d, n, vec_topk, nprobe, d_bitset,
+                                              bitset_nbits, ws->h_out_i.as<int64_t>() + q0 * vec_topk,
+                                              ws->h_out_d.as<float>() + q0 * vec_topk, s, nullptr, nullptr)) {
+                    return r;
+                }
+            }
+            HIP_TRY(hipMemcpyAsync(ids.data(), ws->h_out_i.p, ids.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        // ---- the candidate documents of every list, in the reference's arrival order (see include/knhip.h)
+        std::vector<int64_t> cand_lims((size_t)nel + 1, 0), cand_docs, doc_lims(1, 0), labels;
+        std::unordered_set<size_t> el_ids;
+        for (int64_t e = 0; e < nel; e++) {
+            el_ids.clear();
+            for (int64_t j = q_lims[e] * vec_topk; j < q_lims[e + 1] * vec_topk; j++) {
+                if (ids[(size_t)j] < 0) {
+                    continue;
+                }
+                el_ids.emplace((size_t)(std::upper_bound(doc_offsets, doc_offsets + ndocs + 1, ids[(size_t)j]) - doc_offsets) - 1);
+            }
+            for (const size_t el : el_ids) {
+                if (el >= (size_t)ndocs) {
+                    return fail(KNHIP_ERR_INVALID_ARGS, "emb_list_search: invalid emb_list id " + std::to_string(el) +
+                                                                " (a stored id outside doc_offsets)");
+                }
+                const int64_t lo = doc_offsets[el], hi = doc_offsets[el + 1];
+                if (hi == lo) {
+                    continue; // (an empty document is never scored)
+                }
+                cand_docs.push_back((int64_t)el);
+                for (int64_t v = lo; v < hi; v++) {
+                    labels.push_back(v);
+                }
+                doc_lims.push_back((int64_t)labels.size());
+            }
+            cand_lims[(size_t)e + 1] = (int64_t)cand_docs.size();
+        }
+        // ---- stage 2: every list's candidates in one enqueue, one read-back
+        std::vector<float> scores(cand_docs.size());
+        if (!cand_docs.empty()) {
+            if (int rc = maxsim_host_run(idx, ws, ws->h_queries.as<float>(), q_lims, nel, cand_lims.data(), doc_lims.data(),
+                                         labels.data(), scores.data(), s)) {
+                return rc;
+            }
+        }
+        for (int64_t e = 0; e < nel; e++) {
+            const int64_t c0 = cand_lims[(size_t)e], n = cand_lims[(size_t)e + 1] - c0;
+            if (idx->is_l2) {
+                select_docs<false>(cand_docs.data() + c0, scores.data() + c0, n, k, out_doc_ids + e * k, out_scores + e * k);
+            } else {
+                select_docs<true>(cand_docs.data() + c0, scores.data() + c0, n, k, out_doc_ids + e * k, out_scores + e * k);
+            }
+        }
+        return KNHIP_OK;
+    };
+    const int rc = run();
+    if (rc != KNHIP_OK) {
+        (void)hipStreamSynchronize(s);
+    }
+    release_ws(idx, ws);
+    (void)hipStreamDestroy(s);
+    return rc;
 }
 
 // ---- sharded refine: distances where the rows are, ONE selection over all of them --------------------------------------------

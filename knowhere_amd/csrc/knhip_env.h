@@ -7,7 +7,7 @@
 //   * LAYOUT switches: read when an index lays out its lists / takes its rows / takes its coarse quantizer -- the index keeps
 //     what it read, a later change of the variable does not touch an existing index;
 //   * SEARCH switches: read by every search (tests flip them between two searches of one index: KNHIP_TIES,
-//     KNHIP_RANGE_NO_WAVES, KNHIP_LARGEK_ROUND_KB) -- nine lookups per call.
+//     KNHIP_RANGE_NO_WAVES, KNHIP_LARGEK_ROUND_KB, KNHIP_MAXSIM_ROUND_KB) -- ten lookups per call.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -44,6 +44,7 @@ struct EnvSearch {
     bool ties_trace;       // KNHIP_TIES_TRACE: one line per flagged batch on stderr
     int pqd_unit_cost;     // KNHIP_PQD_UNIT_COST=n: decode-form units cut at n tiles x query tiles (0 = list-long units)
     size_t largek_round_bytes; // KNHIP_LARGEK_ROUND_KB=n: distance dump of one round of a k > 1024 search (default 2 GiB)
+    size_t maxsim_round_bytes; // KNHIP_MAXSIM_ROUND_KB=n: extrema scratch of one round of a MaxSim call (default 256 MiB)
 };
 constexpr int KNHIP_PQD_UNIT_COST_DEFAULT = 512;
 
@@ -121,6 +122,8 @@ inline EnvSearch env_search() {
     e.pqd_unit_cost = (uc && *uc) ? std::max(0, std::atoi(uc)) : KNHIP_PQD_UNIT_COST_DEFAULT;
     const char* lk = std::getenv("KNHIP_LARGEK_ROUND_KB");
     e.largek_round_bytes = (lk && *lk) ? (size_t)std::max<long long>(1, std::atoll(lk)) << 10 : (size_t)2 << 30;
+    const char* mx = std::getenv("KNHIP_MAXSIM_ROUND_KB");
+    e.maxsim_round_bytes = (mx && *mx) ? (size_t)std::max<long long>(1, std::atoll(mx)) << 10 : (size_t)256 << 20;
     return e;
 }
 

@@ -156,6 +156,7 @@ struct Workspace {
     DevBuf h_queries, h_bitset, h_out_d, h_out_i, h_ref_d, h_ref_i;
     DevBuf tie_d, tie_i, tie_flag, tie_q, tie_r, tie_keys, tie_cdis; // search_batch_ties: k + 1 results, flagged queries
     DevBuf tie_arr_d, tie_arr_i, tie_arr_n;                          // ... their first k arrivals
+    DevBuf mx_ext, mx_lims, mx_labels, mx_scores, mx_abs;           // MaxSim: extrema keys of a round; the host forms' uploads and results
     DevBuf lk_plan, lk_scratch;                                      // k > 1024: layout of the compact dump, sort scratch of the ordered top-k
     std::mutex mu;  // held while a *_device entry point enqueues on this (per-stream) workspace
     // side stream of the IVF-PQ prefilter: the grouping of the pairs by list (work table) runs beside the sample pass

@@ -594,8 +594,30 @@ hipError_t launch_rows_encode_i8(const float* x, int64_t n_elems, uint8_t* out, 
 // Zero-padded dimensions (d % 4, typed rows d % 8) take the steps the scans take on them.
 constexpr int CD_PITCH = CD_ROWS + 1;
 
+// column of a label's row in the resident store (BRUTE_FORCE: the row number), -1 = not stored here
+__device__ __forceinline__ int64_t cd_locate(const CalcDistArgs& a, int64_t id) {
+    if (a.idmap_ids == nullptr) {
+        const uint64_t r = (uint64_t)id - (uint64_t)a.id_offset;
+        return r < (uint64_t)a.ntotal ? (int64_t)r : -1;
+    }
+    int64_t lo = 0, hi = a.ntotal;
+    while (lo < hi) { // first entry >= id
+        const int64_t mid = (lo + hi) >> 1;
+        if (a.idmap_ids[mid] < id) {
+            lo = mid + 1;
+        } else {
+            hi = mid;
+        }
+    }
+    return (lo < a.ntotal && a.idmap_ids[lo] == id) ? a.idmap_col[lo] : -1;
+}
+
+// The tile's contraction, shared by calc_dist_kernel and maxsim_score_kernel: the rows s_col[0 .. CD_ROWS) (located by the
+// caller, a barrier behind it) against the queries q0 .. q0 + CD_QT of a.queries, acc[jq] = the running sum of this wave's
+// query jq and this lane's row.  Called by the whole workgroup.
 template <bool IS_L2, int RT>
-__global__ __launch_bounds__(256) void calc_dist_kernel(const CalcDistArgs a) {
+__device__ __forceinline__ void cd_tile_steps(const CalcDistArgs& a, int64_t q0, int nqw, const int64_t* s_col,
+                                              float (&acc)[CD_QT / 4]) {
     constexpr int CDIMS = RT == KN_ROW_FP32 ? 4 : 8;    // dimensions per 16-byte chunk
     constexpr int NCP = CD_DIMS / CDIMS;                // chunks per pass
     constexpr int NPT = CD_ROWS * NCP / 256;            // pieces per thread and pass
@@ -603,48 +625,8 @@ __global__ __launch_bounds__(256) void calc_dist_kernel(const CalcDistArgs a) {
     __shared__ uint4 s_rows[NCP * CD_PITCH];
     __shared__ float4 s_q4[CD_QT * CD_DIMS / 4]; // (16-byte aligned by its type: the waves read it in 16-byte pieces)
     float* s_q = reinterpret_cast<float*>(s_q4);
-    __shared__ int64_t s_col[CD_ROWS];
     const int lane = lane_id();
     const int wave = threadIdx.x / KN_WAVE;
-    const int64_t j0 = (int64_t)blockIdx.x * CD_ROWS;   // first label of the tile
-    const int64_t q0 = (int64_t)blockIdx.y * CD_QT;     // first query
-    // ---- locate the rows: column of the interleaved store (BRUTE_FORCE: the row number), -1 = not stored here
-    if (threadIdx.x < CD_ROWS) {
-        const int64_t j = j0 + threadIdx.x;
-        int64_t col = -1;
-        if (j < a.nlabels) {
-            const int64_t id = a.labels[j];
-            if (a.idmap_ids == nullptr) {
-                const uint64_t r = (uint64_t)id - (uint64_t)a.id_offset;
-                col = r < (uint64_t)a.ntotal ? (int64_t)r : -1;
-            } else {
-                int64_t lo = 0, hi = a.ntotal;
-                while (lo < hi) { // first entry >= id
-                    const int64_t mid = (lo + hi) >> 1;
-                    if (a.idmap_ids[mid] < id) {
-                        lo = mid + 1;
-                    } else {
-                        hi = mid;
-                    }
-                }
-                if (lo < a.ntotal && a.idmap_ids[lo] == id) {
-                    col = a.idmap_col[lo];
-                }
-            }
-            if (col < 0 && a.count_absent && blockIdx.y == 0) {
-                if (a.nabsent != nullptr) {
-                    atomicAdd(a.nabsent, 1ull);
-                }
-                if (a.first_absent != nullptr) {
-                    atomicMin(a.first_absent, (unsigned long long)(a.label_base + j));
-                }
-            }
-        }
-        s_col[threadIdx.x] = col;
-    }
-    __syncthreads();
-    const int nqw = (int)max((int64_t)0, min((int64_t)QW, a.nq - q0 - wave * QW)); // live queries of this wave
-    float acc[QW];
 #pragma unroll
     for (int jq = 0; jq < QW; jq++) {
         acc[jq] = 0.f;
@@ -718,6 +700,37 @@ __global__ __launch_bounds__(256) void calc_dist_kernel(const CalcDistArgs a) {
             }
         }
     }
+}
+
+template <bool IS_L2, int RT>
+__global__ __launch_bounds__(256) void calc_dist_kernel(const CalcDistArgs a) {
+    constexpr int QW = CD_QT / 4;                       // queries per wave
+    __shared__ int64_t s_col[CD_ROWS];
+    const int lane = lane_id();
+    const int wave = threadIdx.x / KN_WAVE;
+    const int64_t j0 = (int64_t)blockIdx.x * CD_ROWS;   // first label of the tile
+    const int64_t q0 = (int64_t)blockIdx.y * CD_QT;     // first query
+    // ---- locate the rows: column of the interleaved store (BRUTE_FORCE: the row number), -1 = not stored here
+    if (threadIdx.x < CD_ROWS) {
+        const int64_t j = j0 + threadIdx.x;
+        int64_t col = -1;
+        if (j < a.nlabels) {
+            col = cd_locate(a, a.labels[j]);
+            if (col < 0 && a.count_absent && blockIdx.y == 0) {
+                if (a.nabsent != nullptr) {
+                    atomicAdd(a.nabsent, 1ull);
+                }
+                if (a.first_absent != nullptr) {
+                    atomicMin(a.first_absent, (unsigned long long)(a.label_base + j));
+                }
+            }
+        }
+        s_col[threadIdx.x] = col;
+    }
+    __syncthreads();
+    const int nqw = (int)max((int64_t)0, min((int64_t)QW, a.nq - q0 - wave * QW)); // live queries of this wave
+    float acc[QW];
+    cd_tile_steps<IS_L2, RT>(a, q0, nqw, s_col, acc);
     // ---- lane = row: one coalesced 256-byte store per query
     const int64_t j = j0 + lane;
     if (j >= a.nlabels) {
@@ -781,6 +794,187 @@ hipError_t launch_calc_dist(const CalcDistArgs& args, bool is_l2, int row_type, 
         }
     }
     return hipSuccess;
+}
+
+// ---- MaxSim: the scores of candidate DOCUMENTS (runs of labels) against a query list, the nq x L matrix never written -------
+// Replaces the reference's rerank loop for the MAX_SIM* metrics (src/index/emb_list/emb_list_strategy.cc:45-117: one
+// CalcDistByStorageIds per candidate document, then get_sum_max_sim, include/knowhere/emb_list_utils.h:123-176): per query i
+// the extremum over the document's rows under a STRICT compare starting from -FLT_MAX (L2: +FLT_MAX, `<`) -- so a NaN or
+// -inf (L2: +inf) distance is never taken --, then score = 0.0f, score += m_i for i ascending.
+// maxsim_score_kernel is calc_dist_kernel's tile (cd_tile_steps: the same loads, the same steps, the same bits) over the
+// labels doc_lims[c_lo] .. doc_lims[c_hi] of ONE query list with another epilogue: every label carries the slot of its
+// document (a binary search of doc_lims), the 64 lanes of a wave run a segmented scan of the extremum per query -- slots
+// are non-decreasing over the lanes, so a segment is a run of lanes -- and the last lane of every run combines the run's
+// extremum into ext[slot][query] as an order-preserving key (common.h): a plain store where the document lies wholly inside
+// the tile, else one atomicMin per (run, query, tile).  Values the strict compare drops never become a key; a run that kept
+// nothing writes nothing (ext starts at the key of -/+FLT_MAX: maxsim_init_kernel).  A label that is not stored marks its
+// document: the all-ones pattern goes to out_scores[c] (zeroed by the init kernel), which maxsim_sum_kernel leaves alone.
+// maxsim_sum_kernel: one thread per document, the fp32 adds over i ascending.
+template <bool IS_L2, int RT>
+__global__ __launch_bounds__(256) void maxsim_score_kernel(const MaxSimArgs m) {
+    constexpr int QW = CD_QT / 4;
+    __shared__ int64_t s_col[CD_ROWS];
+    __shared__ int32_t s_slot[CD_ROWS]; // document of the label, counted from c_lo; -1: no label; bit 30: wholly inside this tile
+    const int lane = lane_id();
+    const int wave = threadIdx.x / KN_WAVE;
+    const CalcDistArgs& a = m.cd;
+    const int64_t lab_lo = m.doc_lims[m.c_lo];
+    const int64_t lab_hi = min(m.doc_lims[m.c_hi], a.nlabels);
+    const int64_t j0 = lab_lo + (int64_t)blockIdx.x * CD_ROWS; // first label of the tile
+    const int64_t q0 = (int64_t)blockIdx.y * CD_QT;            // first query of the list
+    if (lab_lo < 0 || j0 >= lab_hi) {
+        return; // (the whole workgroup: the grid covers an upper bound where the host does not know doc_lims)
+    }
+    if (threadIdx.x < CD_ROWS) {
+        const int64_t j = j0 + threadIdx.x;
+        int64_t col = -1;
+        int32_t slot = -1;
+        if (j < lab_hi) {
+            int64_t lo = m.c_lo + 1, hi = m.c_hi; // first document boundary behind j: doc_lims[c_hi] >= lab_hi > j
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (m.doc_lims[mid] <= j) {
+                    lo = mid + 1;
+                } else {
+                    hi = mid;
+                }
+            }
+            const int64_t c = lo - 1;
+            slot = (int32_t)(c - m.c_lo);
+            if (m.doc_lims[c] >= j0 && m.doc_lims[c + 1] <= j0 + CD_ROWS) {
+                slot |= 1 << 30;
+            }
+            col = cd_locate(a, a.labels[j]);
+            if (col < 0 && blockIdx.y == 0) {
+                m.out_scores[c] = __uint_as_float(REFINE_NOT_HERE); // (every writer stores this one pattern)
+                if (a.nabsent != nullptr) {
+                    atomicAdd(a.nabsent, 1ull);
+                }
+                if (a.first_absent != nullptr) {
+                    atomicMin(a.first_absent, (unsigned long long)j);
+                }
+            }
+        }
+        s_col[threadIdx.x] = col;
+        s_slot[threadIdx.x] = slot;
+    }
+    __syncthreads();
+    const int nqw = (int)max((int64_t)0, min((int64_t)QW, a.nq - q0 - wave * QW)); // live queries of this wave
+    float acc[QW];
+    cd_tile_steps<IS_L2, RT>(a, q0, nqw, s_col, acc);
+    // ---- epilogue: every lane of the wave takes part in the exchanges
+    const int64_t col = s_col[lane];
+    const int32_t sw = s_slot[lane];
+    const int32_t slot = sw < 0 ? -1 : (sw & ~(1 << 30));
+    const bool whole = sw >= 0 && (sw & (1 << 30)) != 0;
+    float sc = 1.0f;
+    if (!IS_L2 && a.cos_mode != 0 && col >= 0) {
+        sc = a.row_scale[col];
+    }
+    bool same[6]; // the lane 2^s below belongs to the same document
+#pragma unroll
+    for (int s = 0; s < 6; s++) {
+        const int32_t o = __shfl_up(slot, 1u << s, KN_WAVE);
+        same[s] = lane >= (1 << s) && o == slot;
+    }
+    const int32_t nxt = __shfl_down(slot, 1u, KN_WAVE);
+    const bool last = slot >= 0 && (lane == KN_WAVE - 1 || nxt != slot); // the run's last lane holds the run's extremum
+    const float none = worst_dist<IS_L2>();
+#pragma unroll
+    for (int jq = 0; jq < QW; jq++) {
+        if (jq < nqw) { // (wave-uniform)
+            float dis = acc[jq];
+            if (!IS_L2 && a.cos_mode != 0) { // COSINE with stored norms (FlatScanArgs)
+                dis = cosine_finish(dis, sc, a.cos_mode);
+            }
+            // the reference's compare against its start value: NaN, -inf (L2: +inf) and -/+FLT_MAX itself are not taken
+            float v = (slot >= 0 && col >= 0 && (IS_L2 ? dis < none : dis > none)) ? dis : none;
+#pragma unroll
+            for (int s = 0; s < 6; s++) {
+                const float o = __shfl_up(v, 1u << s, KN_WAVE);
+                if (same[s] && (IS_L2 ? o < v : o > v)) {
+                    v = o;
+                }
+            }
+            if (last && v != none) {
+                uint32_t* e = m.ext + (int64_t)slot * a.nq + (q0 + wave * QW + jq);
+                const uint32_t key = cr_key_fwd<IS_L2>(v);
+                if (whole) {
+                    *e = key;
+                } else {
+                    atomicMin(e, key);
+                }
+            }
+        }
+    }
+}
+
+template <bool IS_L2>
+__global__ void maxsim_init_kernel(uint32_t* __restrict__ ext, int64_t next, float* __restrict__ out, int64_t ncand) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < next) {
+        ext[t] = cr_key_fwd<IS_L2>(worst_dist<IS_L2>());
+    }
+    if (t < ncand) {
+        out[t] = 0.f;
+    }
+}
+
+template <bool IS_L2>
+__global__ void maxsim_sum_kernel(const uint32_t* __restrict__ ext, int64_t ncand, int64_t nq, float* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ncand || __float_as_uint(out[t]) == REFINE_NOT_HERE) { // (a document with an absent label keeps its mark)
+        return;
+    }
+    float score = 0.0f;
+    for (int64_t i = 0; i < nq; i++) {
+        score = fadd_x(score, cr_unkey_fwd<IS_L2>(ext[t * nq + i]));
+    }
+    out[t] = score;
+}
+
+hipError_t launch_maxsim(const MaxSimArgs& m, bool is_l2, int row_type, int64_t ntiles, hipStream_t s) {
+    const int64_t ncand = m.c_hi - m.c_lo;
+    if (ncand <= 0) {
+        return hipSuccess;
+    }
+    const CalcDistArgs& a = m.cd;
+    const int64_t nqt = std::max<int64_t>(1, (a.nq + CD_QT - 1) / CD_QT); // (a list without queries still locates its labels)
+    if (row_type < KN_ROW_FP32 || row_type > KN_ROW_BF16 || (a.aos && row_type != KN_ROW_FP32) || a.nq < 0 || nqt > 65535 ||
+        ncand >= ((int64_t)1 << 30) || ntiles < 0 || ntiles > 0x7fffffffll || (a.nq > 0 && m.ext == nullptr) ||
+        (!is_l2 && a.cos_mode != 0 && a.row_scale == nullptr)) {
+        return hipErrorInvalidValue;
+    }
+    const int64_t next = ncand * a.nq;
+    const unsigned gi = (unsigned)((std::max(next, ncand) + 255) / 256);
+    const unsigned gs = (unsigned)((ncand + 255) / 256);
+    float* out = m.out_scores + m.c_lo;
+    if (is_l2) {
+        hipLaunchKernelGGL(maxsim_init_kernel<true>, dim3(gi), dim3(256), 0, s, m.ext, next, out, ncand);
+    } else {
+        hipLaunchKernelGGL(maxsim_init_kernel<false>, dim3(gi), dim3(256), 0, s, m.ext, next, out, ncand);
+    }
+    if (ntiles > 0) {
+        const dim3 grid((unsigned)ntiles, (unsigned)nqt);
+#define KN_MX_LAUNCH(RT_)                                                                                  \
+    if (is_l2) {                                                                                           \
+        hipLaunchKernelGGL((maxsim_score_kernel<true, RT_>), grid, dim3(256), 0, s, m);                    \
+    } else {                                                                                               \
+        hipLaunchKernelGGL((maxsim_score_kernel<false, RT_>), grid, dim3(256), 0, s, m);                   \
+    }
+        switch (row_type) {
+            case KN_ROW_FP16: KN_MX_LAUNCH(KN_ROW_FP16); break;
+            case KN_ROW_BF16: KN_MX_LAUNCH(KN_ROW_BF16); break;
+            default: KN_MX_LAUNCH(KN_ROW_FP32); break;
+        }
+#undef KN_MX_LAUNCH
+    }
+    if (is_l2) {
+        hipLaunchKernelGGL(maxsim_sum_kernel<true>, dim3(gs), dim3(256), 0, s, m.ext, ncand, a.nq, out);
+    } else {
+        hipLaunchKernelGGL(maxsim_sum_kernel<false>, dim3(gs), dim3(256), 0, s, m.ext, ncand, a.nq, out);
+    }
+    return hipGetLastError();
 }
 
 } // namespace knhip

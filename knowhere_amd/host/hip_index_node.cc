@@ -340,6 +340,8 @@ class HipIndexNode : public IndexNode {
         dim_ = dataset->GetDim();
         if (c.dim.has_value() && c.dim.value() != dim_) return Status::invalid_args;
         const std::string metric = c.metric_type.value_or(metric::L2);
+        // (an emb_list metric reaches Train as its sub metric: IndexNode::BuildEmbList, src/index/index_node.cc:480, maps it)
+        if (HipEmbListSubMetric(metric) != nullptr) return Status::invalid_metric_type;
         cosine_ = IsMetricType(metric, metric::COSINE);
         metric_ = IsMetricType(metric, metric::L2) ? KNHIP_L2 : KNHIP_IP;
         metric_name_ = cosine_ ? metric::COSINE : (metric_ == KNHIP_L2 ? metric::L2 : metric::IP);
@@ -883,6 +885,164 @@ class HipIndexNode : public IndexNode {
         return GenResultDataSet(nq, nl, static_cast<const int64_t*>(nullptr), static_cast<const float*>(dis.release()));
     }
 
+    // ---- embedding lists (documents of several vectors; the MAX_SIM* metrics), GPU_HIP_BRUTE_FORCE and GPU_HIP_IVF_FLAT ----
+    // IvfIndexNode::AddEmbList (ivf.cc:846-885): the metric is mapped to its sub metric, the documents' offsets (absolute in
+    // the whole index) are appended, then Add.  Inside a Knowhere tree the offsets are the base class's emb_list_offset_
+    // (created by IndexNode::BuildEmbList, appended with its id map by AppendEmbListOffsetAndIdMap), so the base's meta
+    // serialisation keeps working; the stand-alone build keeps them in the shim's member and starts them at {0}.
+    Status
+    AddEmbList(const DataSetPtr dataset, std::shared_ptr<Config> cfg, const size_t* lims, size_t num_rows,
+               bool use_knowhere_build_pool) override {
+        if constexpr (Kind == KNHIP_IVF_PQ || Kind == KNHIP_IVF_SQ8) {
+            LOG_KNOWHERE_WARNING_ << "AddEmbList not implemented for current index type";
+            return Status::not_implemented;
+        }
+        if (!dataset || !cfg || !lims) return Status::invalid_args;
+        if (!Built()) return Status::empty_index;
+        if (sh_.size() > 1) {
+            LOG_KNOWHERE_WARNING_ << TypeName() << ": emb_list is not supported on a node sharded with gpu_ids";
+            return Status::not_implemented;
+        }
+        auto& config = static_cast<BaseConfig&>(*cfg);
+        if (!TokenAnn(config)) {
+            LOG_KNOWHERE_WARNING_ << TypeName() << ": emb_list_strategy " << config.emb_list_strategy.value() << ": only tokenann";
+            return Status::not_implemented;
+        }
+        const char* sub = HipEmbListSubMetric(config.metric_type.value_or(""));
+        if (sub == nullptr) {
+            LOG_KNOWHERE_WARNING_ << "Invalid metric type for emb_list: " << config.metric_type.value_or("");
+            return Status::emb_list_inner_error;
+        }
+        if (!IsMetricType(sub, metric_name_)) return Status::invalid_metric_type;  // (the index was trained for another one)
+        config.metric_type = sub;
+#if defined(KNHIP_WITH_KNOWHERE_HEADERS)
+        if (this->emb_list_offset_ == nullptr || this->emb_list_offset_->offset.empty()) {
+            LOG_KNOWHERE_WARNING_ << "emb_list offset is empty, should call BuildEmbList first";
+            return Status::emb_list_inner_error;
+        }
+        {
+            std::unique_lock<std::shared_mutex> lk(rw_);
+            RETURN_IF_ERROR(this->AppendEmbListOffsetAndIdMap(lims, num_rows, 0));
+        }
+#else
+        {
+            std::unique_lock<std::shared_mutex> lk(rw_);
+            if (this->emb_list_offset_ == nullptr) {
+                this->emb_list_offset_ = std::make_shared<EmbListOffset>();
+                this->emb_list_offset_->offset.push_back(0);
+            }
+            auto& off = this->emb_list_offset_->offset;
+            const size_t total = off.back() + num_rows;
+            if (lims[0] != off.back()) return Status::emb_list_inner_error;  // (not continuous)
+            size_t n = 0;
+            while (lims[n] < total) {
+                if (lims[n + 1] < lims[n]) return Status::emb_list_inner_error;  // (not increasing)
+                n++;
+            }
+            if (lims[n] != total) return Status::emb_list_inner_error;  // (must end with the row count of the whole index)
+            off.insert(off.end(), lims + 1, lims + n + 1);
+        }
+#endif
+        if (num_rows == 0) return Status::success;
+        return Add(dataset, std::move(cfg), use_knowhere_build_pool);
+    }
+
+    std::optional<size_t>
+    GetQueryCodeSize(const DataSetPtr dataset) const override {
+        return (size_t)dataset->GetDim() * sizeof(float);
+    }
+
+    // IndexNode::SearchEmbList (src/index/index_node.cc:252-272) with TokenANNEmbListStrategy::Search (src/index/emb_list/
+    // emb_list_strategy_token_ann.cc:51-175) behind it, as ONE call of the backend: knhip_emb_list_search runs the first-round
+    // search of every query vector, scores every list's candidate documents in one enqueue (refine.hip, maxsim_score_kernel)
+    // where the reference calls CalcDistByStorageIds once per candidate document, and selects k per list by the reference's
+    // heap.  vec_topk = min(max((int)(k * retrieval_ann_ratio), 1), stored vectors).  COSINE: the queries are normalised as
+    // CalcDistByStorageIds normalises them.  The bitset is over storage (vector) ids.  Served: MAX_SIM, MAX_SIM_COSINE,
+    // MAX_SIM_IP, MAX_SIM_L2; DTW* and the binary sub metrics are refused.  not_implemented: IVF_PQ / IVF_SQ8, a node
+    // sharded with gpu_ids, a strategy other than tokenann.
+    expected<DataSetPtr>
+    SearchEmbList(const DataSetPtr dataset, std::unique_ptr<Config> cfg, const BitsetView& bitset,
+                  milvus::OpContext* op_context) const override {
+        using R = expected<DataSetPtr>;
+        if constexpr (Kind == KNHIP_IVF_PQ || Kind == KNHIP_IVF_SQ8) {
+            return R::Err(Status::not_implemented, "SearchEmbList not implemented for current index type");
+        }
+        if (!dataset || !cfg || (dataset->GetRows() > 0 && !dataset->GetTensor())) {
+            return R::Err(Status::invalid_args, "null dataset / config");
+        }
+        if (!Built() || Count() == 0) return R::Err(Status::empty_index, "index not built");
+        if (dataset->GetDim() != dim_) return R::Err(Status::invalid_args, "dim mismatch");
+        if (sh_.size() > 1) return R::Err(Status::not_implemented, "emb_list is not supported on a node sharded with gpu_ids");
+        const auto& c = static_cast<const knowhere_config_type&>(*cfg);
+        if (!TokenAnn(c)) return R::Err(Status::not_implemented, "emb_list_strategy: only tokenann is supported");
+        const std::string metric = c.metric_type.value_or("");
+        const char* sub = HipEmbListSubMetric(metric);
+        if (sub == nullptr) return R::Err(Status::emb_list_inner_error, "invalid metric type: " + metric);
+        if (!IsMetricType(sub, metric_name_)) {
+            return R::Err(Status::invalid_args, "the index was built for " + metric_name_ + ", not for " + metric);
+        }
+#if defined(KNHIP_WITH_KNOWHERE_HEADERS)
+        const size_t* lims = dataset->Get<const size_t*>(meta::EMB_LIST_OFFSET);
+#else
+        const size_t* lims = dataset->GetLims();
+#endif
+        if (lims == nullptr) return R::Err(Status::emb_list_inner_error, "missing emb_list offset, could not search");
+        const float ratio = c.retrieval_ann_ratio.value_or(3.0f);
+        if (ratio <= 0.0f) {
+            return R::Err(Status::emb_list_inner_error, "retrieval_ann_ratio could not be less than or equal to 0");
+        }
+        const int64_t nqv = dataset->GetRows();
+        const int64_t k = c.k.value();
+        int64_t nprobe = 1;
+        if constexpr (Kind != KNHIP_BRUTE_FORCE) nprobe = c.nprobe.value_or(default_nprobe_);
+        // the query lists (EmbListOffset(lims, rows), include/knowhere/emb_list_utils.h:30-41)
+        std::vector<int64_t> q_lims;
+        for (size_t i = 0;; i++) {
+            if (i > 0 && lims[i] < lims[i - 1]) return R::Err(Status::invalid_args, "emb_list offsets of the queries descend");
+            q_lims.push_back((int64_t)lims[i]);
+            if ((int64_t)lims[i] >= nqv) break;
+        }
+        if (q_lims.front() != 0 || q_lims.back() != nqv) {
+            return R::Err(Status::invalid_args, "emb_list offsets of the queries must run from 0 to the number of rows");
+        }
+        const int64_t nel = (int64_t)q_lims.size() - 1;
+        checkCancellation(op_context);
+        const float* q = (const float*)dataset->GetTensor();
+        std::vector<float> qn;
+        if (cosine_ && nqv > 0) {
+            qn.assign(q, q + nqv * dim_);
+            NormalizeRows(qn.data(), nqv, dim_);
+            q = qn.data();
+        }
+        std::vector<uint8_t> in_bitset;
+        const uint8_t* bits = nullptr;
+        int64_t nbits = 0;
+        MaterialiseBitset(bitset, &in_bitset, &bits, &nbits);
+        auto ids = std::make_unique<int64_t[]>((size_t)std::max<int64_t>(nel * k, 1));
+        auto dis = std::make_unique<float[]>((size_t)std::max<int64_t>(nel * k, 1));
+        {
+            std::shared_lock<std::shared_mutex> lk(rw_);
+            if (this->emb_list_offset_ == nullptr || this->emb_list_offset_->offset.size() < 2) {
+                return R::Err(Status::emb_list_inner_error, "emb_list_offset not initialized");
+            }
+            const auto& off = this->emb_list_offset_->offset;
+            const std::vector<int64_t> doc_offsets(off.begin(), off.end());
+            const int64_t vec_topk = std::min<int64_t>(std::max<int64_t>((int32_t)(k * ratio), 1), (int64_t)off.back());
+            if (vec_topk > KNHIP_MAX_K) {
+                return R::Err(Status::invalid_args, "k * retrieval_ann_ratio > 16384 is not supported");
+            }
+            const int rc = knhip_emb_list_search(sh_[0].idx.p, doc_offsets.data(), (int64_t)doc_offsets.size() - 1, q, q_lims.data(),
+                                                 nel, (int32_t)k, (int32_t)vec_topk, (int32_t)nprobe, bits, nbits, ids.get(),
+                                                 dis.get());
+            if (rc) return R::Err(ToStatus(rc), knhip_last_error());
+        }
+        auto res = GenResultDataSet(nel, k, ids.release(), dis.release());
+#if defined(KNHIP_WITH_KNOWHERE_HEADERS)
+        this->MapEmbListResultIdsToOutIds(res);  // compact list ids -> public list ids
+#endif
+        return res;
+    }
+
     static bool
     StaticHasRawData(const knowhere::BaseConfig& config, const IndexVersion& /*version*/) {
         // cosine stores normalised vectors (IvfIndexNode::StaticHasRawData semantics, ivf.cc:142-160)
@@ -1421,6 +1581,14 @@ class HipIndexNode : public IndexNode {
     bool
     StoredNormCosine() const {
         return cosine_ && (Kind == KNHIP_BRUTE_FORCE || Kind == KNHIP_IVF_FLAT);
+    }
+
+    // emb_list_strategy unset or "tokenann" (any letter case): the one strategy served
+    static bool
+    TokenAnn(const BaseConfig& c) {
+        std::string t = c.emb_list_strategy.value_or("tokenann");
+        for (auto& ch : t) ch = (char)std::tolower((unsigned char)ch);
+        return t == "tokenann";
     }
 
     static bool

@@ -43,10 +43,22 @@ inline constexpr const char* INDEX_HIP_IVFSQ8 = "GPU_HIP_IVF_SQ8";
 
 // ---- configs: the CPU index's config + the limits of this backend, in the style of
 // src/index/gpu_cuvs/gpu_cuvs_ivf_pq_config.h:27-95 (k: see KNHIP_CONFIG_MAX_K; the cuVS configs stop at 1024, :49-53) -------------------------
+// the sub metric of an embedding-list metric this backend serves (MAX_SIM = MAX_SIM_COSINE), nullptr for any other name
+// (DTW*, the binary sub metrics, a plain metric)
+inline const char*
+HipEmbListSubMetric(const std::string& m) {
+    if (IsMetricType(m, metric::MAX_SIM) || IsMetricType(m, metric::MAX_SIM_COSINE)) return metric::COSINE;
+    if (IsMetricType(m, metric::MAX_SIM_IP)) return metric::IP;
+    if (IsMetricType(m, metric::MAX_SIM_L2)) return metric::L2;
+    return nullptr;
+}
+
+// emb_list: the raw-data kinds (GPU_HIP_BRUTE_FORCE, GPU_HIP_IVF_FLAT) also take the MAX_SIM* metrics (AddEmbList / SearchEmbList)
 inline Status
-HipCheckMetric(const BaseConfig& cfg, PARAM_TYPE param_type, std::string* err_msg) {
+HipCheckMetric(const BaseConfig& cfg, PARAM_TYPE param_type, std::string* err_msg, bool emb_list = false) {
     if (param_type == PARAM_TYPE::TRAIN && cfg.metric_type.has_value()) {
         const std::string& m = cfg.metric_type.value();
+        if (emb_list && HipEmbListSubMetric(m) != nullptr) return Status::success;
         if (!IsMetricType(m, metric::L2) && !IsMetricType(m, metric::IP) && !IsMetricType(m, metric::COSINE)) {
             if (err_msg) *err_msg = "metric type " + m + " not found or not supported, supported: [L2 IP COSINE]";
             return Status::invalid_metric_type;
@@ -220,7 +232,7 @@ struct HipBruteForceConfig : public FlatConfig {
     Status
     CheckAndAdjust(PARAM_TYPE param_type, std::string* err_msg) override {
         RETURN_IF_ERROR(HipCheckRowType(*this, false, err_msg));
-        return HipCheckMetric(*this, param_type, err_msg);
+        return HipCheckMetric(*this, param_type, err_msg, /*emb_list=*/true);
     }
 };
 
@@ -237,7 +249,7 @@ struct HipIvfFlatConfig : public IvfFlatConfig {
     Status
     CheckAndAdjust(PARAM_TYPE param_type, std::string* err_msg) override {
         RETURN_IF_ERROR(HipCheckRowType(*this, true, err_msg));
-        return HipCheckMetric(*this, param_type, err_msg);
+        return HipCheckMetric(*this, param_type, err_msg, /*emb_list=*/true);
     }
 };
 

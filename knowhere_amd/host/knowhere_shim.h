@@ -196,6 +196,11 @@ namespace metric {
 constexpr const char* L2 = "L2";
 constexpr const char* IP = "IP";
 constexpr const char* COSINE = "COSINE";
+// embedding lists: the sum over a query list's vectors of the best sub-metric distance to a document's vectors
+constexpr const char* MAX_SIM = "MAX_SIM";  // = MAX_SIM_COSINE
+constexpr const char* MAX_SIM_COSINE = "MAX_SIM_COSINE";
+constexpr const char* MAX_SIM_IP = "MAX_SIM_IP";
+constexpr const char* MAX_SIM_L2 = "MAX_SIM_L2";
 }  // namespace metric
 inline bool
 IsMetricType(const std::string& str, const knowhere::MetricType& metric_type) {
@@ -517,6 +522,8 @@ class BaseConfig : public Config {
     CFG_INT range_search_k;
     CFG_FLOAT range_filter;
     CFG_BOOL enable_mmap;
+    CFG_FLOAT retrieval_ann_ratio;  // emb_list search: vectors asked of the first (ANN) round per query vector = k * ratio
+    CFG_STRING emb_list_strategy;   // how documents of several vectors are indexed: "tokenann" = every vector
     KNOWHERE_DECLARE_CONFIG(BaseConfig) {
         KNOWHERE_CONFIG_DECLARE_FIELD(dim).allow_empty_without_default().description("vector dim").for_train();
         KNOWHERE_CONFIG_DECLARE_FIELD(metric_type)
@@ -546,6 +553,16 @@ class BaseConfig : public Config {
             .for_static()
             .for_deserialize()
             .for_deserialize_from_file();
+        KNOWHERE_CONFIG_DECLARE_FIELD(retrieval_ann_ratio)
+            .set_default(3.0f)
+            .description("factor for top-k in the first ANNS round, only used for emb_list")
+            .for_search();
+        KNOWHERE_CONFIG_DECLARE_FIELD(emb_list_strategy)
+            .set_default("tokenann")
+            .description("emb_list strategy")
+            .for_train()
+            .for_search()
+            .for_deserialize();
     }
 };
 
@@ -849,6 +866,11 @@ class BinarySet {
 
 class Interrupt;
 
+// document e of an embedding-list index = the stored vectors offset[e] .. offset[e + 1] - 1
+struct EmbListOffset {
+    std::vector<size_t> offset;
+};
+
 // ---- index_node.h ------------------------------------------------------------------------------------------------------------------
 class IndexNode : public Object {
  public:
@@ -916,6 +938,22 @@ class IndexNode : public Object {
     }
     virtual expected<DataSetPtr>
     GetVectorByIds(const DataSetPtr dataset, milvus::OpContext* op_context = nullptr) const = 0;
+    // embedding lists: rows appended with the offsets of the documents they form (lims absolute in the whole index); a search
+    // of query lists (the query dataset's lims) for the k best documents each; bytes of one query vector
+    virtual Status
+    AddEmbList(const DataSetPtr dataset, std::shared_ptr<Config> cfg, const size_t* lims, size_t num_rows,
+               bool use_knowhere_build_pool = true) {
+        return Status::not_implemented;
+    }
+    virtual expected<DataSetPtr>
+    SearchEmbList(const DataSetPtr dataset, std::unique_ptr<Config> cfg, const BitsetView& bitset,
+                  milvus::OpContext* op_context = nullptr) const {
+        return expected<DataSetPtr>::Err(Status::not_implemented, "SearchEmbList not implemented");
+    }
+    virtual std::optional<size_t>
+    GetQueryCodeSize(const DataSetPtr dataset) const {
+        throw std::runtime_error("GetQueryCodeSize not supported for current index type");
+    }
     virtual bool
     HasRawData(const std::string& metric_type) const = 0;
     virtual bool
@@ -971,6 +1009,7 @@ class IndexNode : public Object {
         GetIdMap().MapInToOut(ids, count);
     }
     IdMap id_map_;
+    std::shared_ptr<EmbListOffset> emb_list_offset_;  // embedding-list index: the documents' offsets
 };
 
 // ---- index_node_thread_pool_wrapper.h: bounds the searches in flight on the device -----------------------------------------------
@@ -1010,6 +1049,18 @@ class IndexNodeThreadPoolWrapper : public IndexNode {
                                               milvus::OpContext* op_context) const override {
         Slot s(this);
         return index_node_->CalcDistByStorageIds(dataset, bitset, labels, labels_len, is_cosine, op_context);
+    }
+    Status AddEmbList(const DataSetPtr dataset, std::shared_ptr<Config> cfg, const size_t* lims, size_t num_rows,
+                      bool use_knowhere_build_pool) override {
+        return index_node_->AddEmbList(dataset, std::move(cfg), lims, num_rows, use_knowhere_build_pool);
+    }
+    expected<DataSetPtr> SearchEmbList(const DataSetPtr dataset, std::unique_ptr<Config> cfg, const BitsetView& bitset,
+                                       milvus::OpContext* op_context) const override {
+        Slot s(this);
+        return index_node_->SearchEmbList(dataset, std::move(cfg), bitset, op_context);
+    }
+    std::optional<size_t> GetQueryCodeSize(const DataSetPtr dataset) const override {
+        return index_node_->GetQueryCodeSize(dataset);
     }
     bool HasRawData(const std::string& metric_type) const override { return index_node_->HasRawData(metric_type); }
     bool NeedBitsetExactCount() const override { return index_node_->NeedBitsetExactCount(); }

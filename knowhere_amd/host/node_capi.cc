@@ -225,6 +225,83 @@ int knhip_node_calc_dist_by_ids(void* h, const float* q, int64_t nq, int64_t dim
     return 0;
 }
 
+// An embedding-list index in two steps, as IndexNode::BuildEmbList (src/index/index_node.cc:453-508) does for the tokenann
+// strategy: Train with the metric's sub metric on all the vectors, then IndexNode::AddEmbList with the documents' offsets
+// (lims[0] = 0 .. lims[ndocs] = rows) under the emb_list metric itself.  Returns the Status value (0 = success).
+int knhip_node_build_emb_list(void* h, const float* x, int64_t rows, int64_t dim, const int64_t* lims, int64_t ndocs,
+                              const char* cfg) {
+    auto* node = static_cast<Handle*>(h)->idx.Node();
+    const Status st = Index<IndexNode>::Guard([&] {
+        Json j = ParseConfig(cfg);
+        auto ds = GenDataSet(rows, dim, x);
+        std::string msg;
+        std::shared_ptr<Config> add_cfg = node->CreateConfig();
+        Status s = Index<IndexNode>::LoadConfig(static_cast<BaseConfig*>(add_cfg.get()), j, PARAM_TYPE::TRAIN, &msg);
+        if (s != Status::success) {
+            g_err = msg;
+            return s;
+        }
+        const std::string metric = static_cast<BaseConfig*>(add_cfg.get())->metric_type.value_or("");
+        const char* sub = HipEmbListSubMetric(metric);
+        if (sub == nullptr) {
+            g_err = "invalid metric type for emb_list: " + metric;
+            return Status::emb_list_inner_error;
+        }
+        j["metric_type"] = sub;
+        std::shared_ptr<Config> train_cfg = node->CreateConfig();
+        s = Index<IndexNode>::LoadConfig(static_cast<BaseConfig*>(train_cfg.get()), j, PARAM_TYPE::TRAIN, &msg);
+        if (s != Status::success) {
+            g_err = msg;
+            return s;
+        }
+        RETURN_IF_ERROR(node->Train(ds, train_cfg, true));
+        const std::vector<size_t> l(lims, lims + ndocs + 1);
+        return node->AddEmbList(ds, add_cfg, l.data(), (size_t)rows, true);
+    });
+    return (int)st;
+}
+
+// IndexNode::SearchEmbList: q [nqv][dim] holds nel query lists, list e = rows q_lims[e] .. q_lims[e + 1] - 1 (q_lims[nel] =
+// nqv); ids / scores receive nel * k results (k from the config).  bitset (over vector ids) may be null.
+int knhip_node_search_emb_list(void* h, const float* q, int64_t nqv, int64_t dim, const int64_t* q_lims, int64_t nel,
+                               const char* cfg, const uint8_t* bitset, int64_t nbits, int64_t* ids, float* scores) {
+    auto* node = static_cast<Handle*>(h)->idx.Node();
+    if (!q_lims || nel < 0 || q_lims[0] != 0 || q_lims[nel] != nqv) {
+        // (IndexNode::SearchEmbList reads the offsets up to the entry that equals the number of rows)
+        g_err = "SearchEmbList: the query offsets must run from 0 to the number of query vectors";
+        return (int)Status::invalid_args;
+    }
+    try {
+        auto c = node->CreateConfig();
+        std::string msg;
+        const Status s = Index<IndexNode>::LoadConfig(c.get(), ParseConfig(cfg), PARAM_TYPE::SEARCH, &msg);
+        if (s != Status::success) {
+            g_err = msg;
+            return (int)s;
+        }
+        const int64_t k = c->k.value();
+        const std::vector<size_t> l(q_lims, q_lims + nel + 1);
+        auto ds = GenDataSet(nqv, dim, q);
+        ds->SetLims(l.data());  // (not owned: GenDataSet's datasets own nothing)
+        auto r = node->SearchEmbList(ds, std::move(c), node->PrepareBitset(bitset ? BitsetView(bitset, (size_t)nbits) : BitsetView()),
+                                     nullptr);
+        if (!r.has_value()) {
+            g_err = r.what();
+            return (int)r.error();
+        }
+        if (r.value()->GetRows() != nel || r.value()->GetDim() != k) {
+            g_err = "SearchEmbList: result shape is not rows = number of query lists, dim = k";
+            return (int)Status::knowhere_inner_error;
+        }
+        std::memcpy(ids, r.value()->GetIds(), sizeof(int64_t) * (size_t)(nel * k));
+        std::memcpy(scores, r.value()->GetDistance(), sizeof(float) * (size_t)(nel * k));
+        return 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return (int)Status::knowhere_inner_error;
+    }
+}
+
 // where the index built / loaded last on the calling thread was placed (device ordinals in shard order): test hook
 int32_t knhip_node_last_placement(int32_t* out, int32_t cap) { return knhip_host_last_placement(out, cap); }
 

@@ -330,6 +330,39 @@ class GpuIndex:
         check(self.L.knhip_index_calc_dist(self.h, _np_ptr(xq), xq.shape[0], len(labels), _np_ptr(labels), _np_ptr(out)))
         return out
 
+    def maxsim(self, xq, q_lims, cand_lims, doc_lims, labels):
+        """knhip_index_maxsim -> [number of documents] float32: MaxSim scores of candidate documents.  Query list e = rows
+        q_lims[e] .. q_lims[e+1]-1 of xq, its candidates = documents cand_lims[e] .. cand_lims[e+1]-1, document c = the stored
+        vectors of labels[doc_lims[c] .. doc_lims[c+1]-1]; score = sum over the list's queries, in order, of the best distance
+        to a vector of the document.  A label that is not stored is an error.  BRUTE_FORCE and IVF_FLAT."""
+        xq = np.ascontiguousarray(xq, np.float32).reshape(-1, self.dim)
+        q_lims = np.ascontiguousarray(q_lims, np.int64).reshape(-1)
+        cand_lims = np.ascontiguousarray(cand_lims, np.int64).reshape(-1)
+        doc_lims = np.ascontiguousarray(doc_lims, np.int64).reshape(-1)
+        labels = np.ascontiguousarray(labels, np.int64).reshape(-1)
+        assert len(q_lims) == len(cand_lims) >= 1 and len(doc_lims) >= 1
+        out = np.zeros(len(doc_lims) - 1, np.float32)
+        check(self.L.knhip_index_maxsim(self.h, _np_ptr(xq), _np_ptr(q_lims), len(q_lims) - 1, _np_ptr(cand_lims),
+                                        _np_ptr(doc_lims), _np_ptr(labels), _np_ptr(out)))
+        return out
+
+    def emb_list_search(self, doc_offsets, xq, q_lims, k, vec_topk, nprobe=1, bitset=None, nbits=0):
+        """knhip_emb_list_search (TokenANN) -> (scores [nel, k] float32, document ids [nel, k] int64): document e of the index =
+        the stored ids doc_offsets[e] .. doc_offsets[e+1]-1; one search of all query vectors with k = vec_topk finds each
+        list's candidate documents, MaxSim scores them, the k best per list come back best first (id -1 where fewer).  The
+        bitset (packed bytes, as search) is over stored ids."""
+        xq = np.ascontiguousarray(xq, np.float32).reshape(-1, self.dim)
+        q_lims = np.ascontiguousarray(q_lims, np.int64).reshape(-1)
+        doc_offsets = np.ascontiguousarray(doc_offsets, np.int64).reshape(-1)
+        nel = len(q_lims) - 1
+        D = np.empty((nel, k), np.float32)
+        I = np.empty((nel, k), np.int64)
+        bs = None if bitset is None else np.ascontiguousarray(bitset, np.uint8)
+        nbits = _bitset_nbits(bs, nbits)
+        check(self.L.knhip_emb_list_search(self.h, _np_ptr(doc_offsets), len(doc_offsets) - 1, _np_ptr(xq), _np_ptr(q_lims), nel,
+                                           k, vec_topk, nprobe, _np_ptr(bs), nbits, _np_ptr(I), _np_ptr(D)))
+        return D, I
+
     def last_range_ranks(self):
         """coarse ranks per query the last range_search scanned (rank waves: knhip_index_last_range_ranks)"""
         return int(self.L.knhip_index_last_range_ranks(self.h))
@@ -399,6 +432,21 @@ class GpuIndex:
         check(self.L.knhip_index_calc_dist_device(self.h, _t_ptr(xq_t), nq, nl, _t_ptr(labels_t), _t_ptr(D), _t_ptr(nabsent),
                                                   C.c_void_p(s)))
         return D, nabsent
+
+    def maxsim_device(self, xq_t, q_lims, cand_lims, doc_lims_t, labels_t, out=None, stream=None):
+        """knhip_index_maxsim_device -> (scores [number of documents] float32, nabsent [1] int64), device tensors, enqueued on
+        the stream; q_lims / cand_lims are host arrays.  The score of a document with a label that is not stored here is the
+        all-ones bit pattern."""
+        import torch
+        q_lims = np.ascontiguousarray(q_lims, np.int64).reshape(-1)
+        cand_lims = np.ascontiguousarray(cand_lims, np.int64).reshape(-1)
+        S = torch.zeros(doc_lims_t.shape[0] - 1, dtype=torch.float32, device=xq_t.device) if out is None else out
+        nabsent = torch.zeros(1, dtype=torch.int64, device=xq_t.device)
+        s = torch.cuda.current_stream(xq_t.device).cuda_stream if stream is None else stream
+        check(self.L.knhip_index_maxsim_device(self.h, _t_ptr(xq_t), _np_ptr(q_lims), len(q_lims) - 1, _np_ptr(cand_lims),
+                                               _t_ptr(doc_lims_t), _t_ptr(labels_t), labels_t.shape[0], _t_ptr(S),
+                                               _t_ptr(nabsent), C.c_void_p(s)))
+        return S, nabsent
 
     def search_preassigned_device(self, xq_t, k, keys_t, cdis_t, bitset_t=None, nbits=0, stream=None):
         """search with a given coarse assignment (keys_t / cdis_t: [nq][nprobe] from coarse_search_device)"""

@@ -251,6 +251,10 @@ int knhip_kmeans_device(int32_t metric, int32_t dim, int64_t n, const float* d_x
                         const knhip_train_params* params, float* d_centroids, int32_t device);
 int knhip_index_train(knhip_index* idx, int64_t n, const float* x, const knhip_train_params* params);
 int knhip_index_train_device(knhip_index* idx, int64_t n, const float* d_x, const knhip_train_params* params);
+/* Add, as IndexIVF::add_core (IndexIVF.cpp:241-287).  A row whose distance to every centroid is NaN or infinite -- a NaN or
+ * inf component; under L2 a squared norm that overflows -- has no centroid (assignment -1): it is skipped, yet counted.
+ * ids == NULL: the id of row i is count + i with knhip_index_count as it was before the call, so a skipped row leaves a gap
+ * in the ids and the rows of a later Add keep the numbers the reference gives them. */
 int knhip_index_add(knhip_index* idx, int64_t n, const float* x, const int64_t* ids);
 int knhip_index_add_device(knhip_index* idx, int64_t n, const float* d_x, const int64_t* d_ids);
 /* IVF_FLAT: rows x_store appended to the lists their companions x_assign are assigned to -- IndexIVFFlatCosine::
@@ -258,10 +262,12 @@ int knhip_index_add_device(knhip_index* idx, int64_t n, const float* d_x, const 
 int knhip_index_add_assigned_by(knhip_index* idx, int64_t n, const float* x_store, const float* x_assign,
                                 const int64_t* ids);
 /* quantizer->assign of n HOST rows (IndexIVF::add_core's first step, IndexIVF.cpp:236): assign [n] int64, the list every
- * row would be appended to (first maximum for the inner product, as IndexFlat::assign).  What a node that deals its
+ * row would be appended to (first maximum for the inner product, as IndexFlat::assign), -1 for a row without a centroid
+ * (no distance below FLT_MAX / no product above -FLT_MAX, where the reference's heap starts).  What a node that deals its
  * inverted lists over several devices needs to route a row to the device owning its list. */
 int knhip_index_assign(const knhip_index* idx, int64_t n, const float* x, int64_t* assign);
-/* assignment + codes of n device rows without adding them: d_assign [n] int64, d_codes [n][code_size] */
+/* assignment + codes of n device rows without adding them: d_assign [n] int64, d_codes [n][code_size]; the codes of a row
+ * with assignment -1 mean nothing */
 int knhip_index_encode_device(const knhip_index* idx, int64_t n, const float* d_x, int64_t* d_assign, uint8_t* d_codes,
                               void* stream);
 /* read the trained state / the inverted lists back (host buffers): Serialize needs the faiss objects
@@ -276,7 +282,18 @@ int knhip_index_get_lists(const knhip_index* idx, uint8_t* codes, int64_t* ids);
 int knhip_index_get_vectors_device(const knhip_index* idx, const float** d_rows);
 
 int knhip_index_get_desc(const knhip_index* idx, knhip_desc* out);  /* the descriptor the index was created with */
-int64_t knhip_index_count(const knhip_index* idx);         /* stored vectors */
+/* The reference's IndexIVF::ntotal, what IvfIndexNode::Count returns (src/index/ivf/ivf.cc:336-341): the rows OFFERED to
+ * knhip_index_add*, the rows without a centroid (skipped, not stored) included -- IndexIVF::add_core ends with ntotal += n
+ * whatever it skipped (IndexIVF.cpp:286).  Without such rows, and after knhip_index_add_lists / knhip_index_set_lists_device /
+ * knhip_index_add_vectors*, which replace the contents, it is the number of stored vectors.  The number STORED in an IVF index
+ * is always the sum of knhip_index_get_list_sizes: buffers for knhip_index_get_lists are sized by that sum, not by count.
+ * The iterator's T (below) is computed from the stored rows. */
+int64_t knhip_index_count(const knhip_index* idx);
+/* IVF kinds, additive to ABI 9: what a loader calls after knhip_index_add_lists / knhip_index_set_lists_device to restore
+ * the ntotal of the index it read, where that index had skipped rows -- the serialized header carries IndexIVF::ntotal, the
+ * rows offered, which the lists alone do not tell.  count >= the rows stored, else KNHIP_ERR_INVALID_ARGS.  The default ids
+ * of a later knhip_index_add* start there. */
+int knhip_index_set_count(knhip_index* idx, int64_t count);
 int64_t knhip_index_device_bytes(const knhip_index* idx);  /* HBM held by the index */
 int knhip_index_uses_precomputed_table(const knhip_index* idx);
 

@@ -43,7 +43,7 @@ SYMBOLS = [
     "knhip_abi_version", "knhip_device_count", "knhip_last_error", "knhip_index_create",
     "knhip_index_destroy", "knhip_index_set_coarse", "knhip_index_set_pq", "knhip_index_set_sq", "knhip_index_set_sq_type", "knhip_index_get_sq_type", "knhip_index_set_row_type", "knhip_index_get_row_type", "knhip_index_set_row_scale", "knhip_index_add_assigned_by", "knhip_index_get_desc",
     "knhip_index_add_lists", "knhip_index_add_vectors", "knhip_index_set_coarse_device",
-    "knhip_index_set_lists_device", "knhip_index_add_vectors_device", "knhip_index_count",
+    "knhip_index_set_lists_device", "knhip_index_add_vectors_device", "knhip_index_count", "knhip_index_set_count",
     "knhip_index_device_bytes", "knhip_index_uses_precomputed_table", "knhip_index_last_range_ranks", "knhip_search",
     "knhip_search_device", "knhip_coarse_search_device", "knhip_merge_topk_device",
     "knhip_search_canonical_device", "knhip_ties_rule_applies", "knhip_tie_flag_device", "knhip_tie_arrivals_device", "knhip_tie_resolve_device",
@@ -152,6 +152,8 @@ def load():
     L.knhip_index_add_vectors.argtypes = [vp, i64, vp, vp, i64]
     L.knhip_index_add_vectors_device.argtypes = [vp, i64, vp, vp, i64]
     L.knhip_index_count.argtypes = [vp]
+    if hasattr(L, "knhip_index_set_count"):  # (a KNHIP_LIB library may predate it)
+        L.knhip_index_set_count.argtypes = [vp, i64]
     L.knhip_index_device_bytes.argtypes = [vp]
     L.knhip_index_uses_precomputed_table.argtypes = [vp]
     L.knhip_index_last_range_ranks.argtypes = [vp]

@@ -184,7 +184,8 @@ hipError_t launch_residual(const float* x, const float* cen, const int64_t* assi
 template <class OutT>
 __global__ __launch_bounds__(256) void nearest_small_kernel(const float* __restrict__ x, int64_t n, int64_t ld, int off,
                                                             int dsub, const float* __restrict__ cb, int ksub,
-                                                            OutT* __restrict__ out, int64_t out_ld) {
+                                                            OutT* __restrict__ out, int64_t out_ld,
+                                                            float* __restrict__ out_dis) {
     extern __shared__ float s_cb[]; // [ksub][dsub]
     const int book = blockIdx.y;
     const float* cbm = cb + (int64_t)book * ksub * dsub;
@@ -233,10 +234,13 @@ __global__ __launch_bounds__(256) void nearest_small_kernel(const float* __restr
         }
     }
     out[i * out_ld + book] = (OutT)best;
+    if (out_dis != nullptr) { // (nbook = 1: k-means' objective)
+        out_dis[i] = best_d;
+    }
 }
 
 hipError_t launch_nearest_small(const float* x, int64_t n, int64_t ld, int off, int dsub, const float* cb, int ksub,
-                                int32_t* out_idx, hipStream_t s) {
+                                int32_t* out_idx, float* out_dis, hipStream_t s) {
     if (n <= 0) {
         return hipSuccess;
     }
@@ -250,7 +254,7 @@ hipError_t launch_nearest_small(const float* x, int64_t n, int64_t ld, int off, 
         }
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256), 1), dim3(256), sm, s, x, n, ld, off, dsub, cb, ksub, out_idx,
-                       (int64_t)1);
+                       (int64_t)1, out_dis);
     return hipGetLastError();
 }
 
@@ -269,7 +273,7 @@ hipError_t launch_pq_encode(const float* resid, int64_t n, int d, int M, const f
         }
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256), (unsigned)M), dim3(256), sm, s, resid, n, (int64_t)d, 0, dsub,
-                       cb, 256, codes, (int64_t)M);
+                       cb, 256, codes, (int64_t)M, (float*)nullptr);
     return hipGetLastError();
 }
 
@@ -402,14 +406,17 @@ hipError_t launch_col_minmax(const float* x, int64_t n, int d, float* vmin, floa
 }
 
 // ---- k-means update ------------------------------------------------------------------------------------------------
-__global__ void keys_to_i32_kernel(const int64_t* __restrict__ keys, int64_t n, int32_t* __restrict__ out,
+// a negative key (a row without a centroid: the reference's assignment answers -1 and add_core skips the row) becomes
+// key nk, behind every group: the radix sort sees only the low bits of a key, and the low bits of -1 are those of the
+// last group whenever nk is a power of two
+__global__ void keys_to_i32_kernel(const int64_t* __restrict__ keys, int64_t n, int32_t nk, int32_t* __restrict__ out,
                                    int32_t* __restrict__ iota, int32_t* counts) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) {
         return;
     }
-    const int32_t k = (int32_t)keys[t];
-    out[t] = k;
+    const int64_t k = keys[t];
+    out[t] = k >= 0 ? (int32_t)k : nk;
     iota[t] = (int32_t)t;
     if (counts != nullptr && k >= 0) {
         atomicAdd(&counts[k], 1);
@@ -438,7 +445,8 @@ size_t group_rows_tmp_bytes(int64_t n, int64_t k) {
 }
 
 // keys (int64 [n], or int32 if keys32 != nullptr) in [0, k) -> rows grouped by key, ascending row number inside a
-// group (stable sort), seg_off[k + 1]
+// group (stable sort), seg_off[k + 1].  int64 keys may be negative: those rows belong to no group, they come behind
+// seg_off[k] in sorted_rows.  (int32 keys are those of nearest_small_kernel, which always names a codeword.)
 hipError_t group_rows_by_key(const int64_t* keys64, const int32_t* keys32_in, int64_t n, int64_t k, int32_t* sorted_rows,
                              int64_t* seg_off, void* tmp, size_t tmp_bytes, hipStream_t s) {
     if (n >= (int64_t)1 << 31 || k >= (int64_t)1 << 31) {
@@ -460,11 +468,12 @@ hipError_t group_rows_by_key(const int64_t* keys64, const int32_t* keys32_in, in
         if (keys32_in != nullptr) {
             hipLaunchKernelGGL(iota_count_kernel, dim3(g), dim3(256), 0, s, keys32_in, n, iota, counts);
         } else {
-            hipLaunchKernelGGL(keys_to_i32_kernel, dim3(g), dim3(256), 0, s, keys64, n, keys32, iota, counts);
+            hipLaunchKernelGGL(keys_to_i32_kernel, dim3(g), dim3(256), 0, s, keys64, n, (int32_t)k, keys32, iota, counts);
         }
     }
+    const int64_t nkeys = keys32_in != nullptr ? k : k + 1; // (key k: the rows without a group)
     int bits = 1;
-    while (((int64_t)1 << bits) < k) {
+    while (((int64_t)1 << bits) < nkeys) {
         bits++;
     }
     size_t b = cub_bytes;
@@ -517,25 +526,34 @@ hipError_t launch_centroid_update(const float* x, int64_t ld, int off, int dsub,
 // spherical renormalisation their products with a row can round to the same float.  One wave per row: rows whose two
 // best candidates tie bit for bit are rescanned over all centroids (sequential exact products, lowest index of the
 // maximum); every other row keeps its best candidate.
+// The reference's heap starts at -FLT_MAX and admits a product only above it: a row whose products are all NaN, -inf or
+// -FLT_MAX has NO centroid, the answer is -1 (IndexIVF::add_core skips such a row).  A row whose best candidate is NaN is
+// rescanned too, so that a NaN never stands for a finite product behind it.
+// out_dis (may be null): the product with the assigned centroid, -FLT_MAX for a row without one (k-means' objective).
 __global__ __launch_bounds__(256) void assign_first_max_ip_kernel(const float* __restrict__ x, int64_t n, int d,
                                                                   const float* __restrict__ cen, int64_t nlist,
                                                                   const int64_t* __restrict__ top2_keys,
                                                                   const float* __restrict__ top2_dis,
-                                                                  int64_t* __restrict__ out) {
+                                                                  int64_t* __restrict__ out, float* __restrict__ out_dis) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
     if (i >= n) {
         return;
     }
     const int64_t k0 = top2_keys[2 * i];
-    if (!(top2_dis[2 * i] == top2_dis[2 * i + 1]) || top2_keys[2 * i + 1] < 0) {
+    const float d0 = top2_dis[2 * i];
+    if (d0 == d0 && (!(d0 == top2_dis[2 * i + 1]) || top2_keys[2 * i + 1] < 0)) {
         if (lane == 0) {
-            out[i] = k0;
+            const bool has = d0 > -FLT_MAX && k0 >= 0;
+            out[i] = has ? k0 : -1;
+            if (out_dis != nullptr) {
+                out_dis[i] = has ? d0 : -FLT_MAX;
+            }
         }
         return;
     }
     const float* xi = x + i * d;
-    float best = -INFINITY;
+    float best = -FLT_MAX;
     int64_t bi = INT64_MAX;
     for (int64_t c = lane; c < nlist; c += 64) {
         const float* cc = cen + c * d;
@@ -558,17 +576,44 @@ __global__ __launch_bounds__(256) void assign_first_max_ip_kernel(const float* _
         }
     }
     if (lane == 0) {
-        out[i] = bi == INT64_MAX ? k0 : bi;
+        out[i] = bi == INT64_MAX ? -1 : bi;
+        if (out_dis != nullptr) {
+            out_dis[i] = best;
+        }
     }
 }
 
 hipError_t launch_assign_first_max_ip(const float* x, int64_t n, int d, const float* cen, int64_t nlist,
-                                      const int64_t* top2_keys, const float* top2_dis, int64_t* out, hipStream_t s) {
+                                      const int64_t* top2_keys, const float* top2_dis, int64_t* out, float* out_dis,
+                                      hipStream_t s) {
     if (n <= 0) {
         return hipSuccess;
     }
     hipLaunchKernelGGL(assign_first_max_ip_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, x, n, d, cen, nlist,
-                       top2_keys, top2_dis, out);
+                       top2_keys, top2_dis, out, out_dis);
+    return hipGetLastError();
+}
+
+// k = 1 search -> IndexFlat::assign: the reference's heap starts at FLT_MAX (L2; -FLT_MAX for the inner product) and admits a
+// distance only below (above) it, so a row whose distances are all NaN, inf or FLT_MAX has no centroid: -1
+__global__ void assign_drop_unreached_kernel(int64_t* __restrict__ assign, float* __restrict__ dis, int64_t n, int is_l2) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) {
+        return;
+    }
+    const float v = dis[i];
+    if (!(is_l2 ? v < FLT_MAX : v > -FLT_MAX)) {
+        assign[i] = -1;
+        dis[i] = is_l2 ? FLT_MAX : -FLT_MAX;
+    }
+}
+
+hipError_t launch_assign_drop_unreached(int64_t* assign, float* dis, int64_t n, bool is_l2, hipStream_t s) {
+    if (n <= 0) {
+        return hipSuccess;
+    }
+    hipLaunchKernelGGL(assign_drop_unreached_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, assign, dis, n,
+                       is_l2 ? 1 : 0);
     return hipGetLastError();
 }
 

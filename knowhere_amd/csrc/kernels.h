@@ -767,7 +767,7 @@ hipError_t launch_gather_rows(const float* x, const int64_t* rows, int64_t n, in
 hipError_t launch_residual(const float* x, const float* cen, const int64_t* assign, int64_t n, int d, float* out,
                            hipStream_t s);
 hipError_t launch_nearest_small(const float* x, int64_t n, int64_t ld, int off, int dsub, const float* cb, int ksub,
-                                int32_t* out_idx, hipStream_t s);
+                                int32_t* out_idx, float* out_dis, hipStream_t s); // out_dis (may be null): the distances [n]
 hipError_t launch_pq_encode(const float* resid, int64_t n, int d, int M, const float* cb, uint8_t* codes, hipStream_t s);
 hipError_t launch_sq8_encode(const float* resid, int64_t n, int d, const float* trained, uint8_t* codes, hipStream_t s);
 // IVF-SQ list codes of any width (bits = 8, 6, 4): codes [n][sq_code_size(d, bits)], the reference's bytes
@@ -784,9 +784,13 @@ hipError_t launch_merge_lists(const uint8_t* old_codes, const int64_t* old_ids, 
                               const int64_t* new_seg, const int64_t* out_off, int64_t nlist, int64_t code_size,
                               uint8_t* out_codes, int64_t* out_ids, hipStream_t s);
 hipError_t launch_iota_i64(int64_t* out, int64_t n, int64_t base, hipStream_t s);
-// k = 1 assignment under the inner product with the reference's first-maximum tie rule (see build.hip)
+// k = 1 assignment under the inner product with the reference's first-maximum tie rule (see build.hip); -1: a row without a
+// centroid.  out_dis (may be null): the products with the assigned centroids [n]
 hipError_t launch_assign_first_max_ip(const float* x, int64_t n, int d, const float* cen, int64_t nlist,
-                                      const int64_t* top2_keys, const float* top2_dis, int64_t* out, hipStream_t s);
+                                      const int64_t* top2_keys, const float* top2_dis, int64_t* out, float* out_dis,
+                                      hipStream_t s);
+// the result of a k = 1 search -> IndexFlat::assign: -1 where the distance never passed the heap's starting value
+hipError_t launch_assign_drop_unreached(int64_t* assign, float* dis, int64_t n, bool is_l2, hipStream_t s);
 // fvec_renorm_L2 of k rows in place; inv_tmp: k floats of scratch
 hipError_t launch_renorm_rows(float* x, int64_t k, int d, float* inv_tmp, hipStream_t s);
 

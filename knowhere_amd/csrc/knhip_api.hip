@@ -296,6 +296,7 @@ int build_list_layout(knhip_index* idx, const std::vector<int64_t>& list_off, co
     const int64_t nlist = idx->nlist;
     const int64_t ntotal = list_off[nlist];
     idx->ntotal = ntotal;
+    idx->noffered = ntotal;   // (Add counts the rows it skipped on top: add_device_impl)
     idx->row_scale.release(); // (stored norms belong to one layout: the caller sets them again after an Add)
     idx->cos_mode = 0;
     idx->h_list_len.resize(nlist);
@@ -1053,6 +1054,7 @@ int add_vectors_common(knhip_index* idx, int64_t n, const float* d_x, const int6
     }
     HIP_TRY(hipDeviceSynchronize());
     idx->ntotal = n;
+    idx->noffered = n;
     idx->id_offset = id_offset;
     idx->has_data = n > 0;
     idx->rg_seg_nseg = -1; // (the segment table of range_segments belongs to the old row count)
@@ -1097,7 +1099,17 @@ int knhip_index_add_vectors_device(knhip_index* idx, int64_t n, const float* d_x
 }
 
 int64_t knhip_index_count(const knhip_index* idx) {
-    return idx ? idx->ntotal : 0;
+    return idx ? idx->noffered : 0;
+}
+
+int knhip_index_set_count(knhip_index* idx, int64_t count) {
+    if (int rc = check_index(idx)) return rc;
+    if (idx->desc.kind == KNHIP_BRUTE_FORCE || count < idx->ntotal) {
+        return fail(KNHIP_ERR_INVALID_ARGS, "set_count: an IVF index, and no less than the rows it stores");
+    }
+    std::lock_guard<std::mutex> lk(idx->add_mu);
+    idx->noffered = count;
+    return KNHIP_OK;
 }
 
 int knhip_index_get_desc(const knhip_index* idx, knhip_desc* out) {

@@ -2,6 +2,9 @@
 // Clustering restated over the kernels of build.hip, encoder training, assignment + encoding + append.
 #include "knhip_internal.h"
 
+#include <cmath>
+#include <limits>
+
 namespace knhip_host {
 
 // faiss RandomGenerator / rand_perm (thirdparty/faiss/faiss/utils/random.cpp:35-55, 188-199): std::mt19937 seeded with
@@ -67,14 +70,22 @@ int split_clusters_host(int d, int64_t k, int64_t n, std::vector<float>& hassign
 // IndexFlat::assign (k = 1 search, first best centroid wins) of n device rows.  L2: the coarse search's canonical order
 // (distance, then id ascending) is the reference's answer.  Inner product: canonical ties come highest id first, the
 // reference keeps the lowest -- rows whose two best candidates tie are rescanned (build.hip).
-int assign_rows(const knhip_index* idx, const float* d_x, int64_t n, int64_t* d_assign, hipStream_t s) {
+// A row whose distance to every centroid is NaN or infinite (a NaN or inf component; under L2 a squared norm that overflows)
+// has no centroid: the reference's heap starts at FLT_MAX (-FLT_MAX) and admits only what is better, its answer is -1, and
+// IndexIVF::add_core skips the row (IndexIVF.cpp:262).  d_dist (may be null): the distance to the assigned centroid [n].
+int assign_rows(const knhip_index* idx, const float* d_x, int64_t n, int64_t* d_assign, hipStream_t s,
+                float* d_dist = nullptr) {
     if (n <= 0) {
         return KNHIP_OK;
     }
     DevBuf dist;
     if (idx->desc.metric != KNHIP_IP || idx->nlist < 2) {
-        HIP_TRY(dist.alloc((size_t)n * sizeof(float)));
-        if (int rc = knhip_coarse_search_device(idx, d_x, n, 1, d_assign, dist.as<float>(), s)) return rc;
+        if (d_dist == nullptr) {
+            HIP_TRY(dist.alloc((size_t)n * sizeof(float)));
+            d_dist = dist.as<float>();
+        }
+        if (int rc = knhip_coarse_search_device(idx, d_x, n, 1, d_assign, d_dist, s)) return rc;
+        HIP_TRY(launch_assign_drop_unreached(d_assign, d_dist, n, idx->desc.metric != KNHIP_IP, s));
         HIP_TRY(hipStreamSynchronize(s)); // (the scratch is freed on return)
         return KNHIP_OK;
     }
@@ -83,7 +94,7 @@ int assign_rows(const knhip_index* idx, const float* d_x, int64_t n, int64_t* d_
     HIP_TRY(keys2.alloc((size_t)n * 2 * sizeof(int64_t)));
     if (int rc = knhip_coarse_search_device(idx, d_x, n, 2, keys2.as<int64_t>(), dist.as<float>(), s)) return rc;
     HIP_TRY(launch_assign_first_max_ip(d_x, n, idx->d, idx->centroids.as<float>(), idx->nlist, keys2.as<int64_t>(),
-                                       dist.as<float>(), d_assign, s));
+                                       dist.as<float>(), d_assign, d_dist, s));
     HIP_TRY(hipStreamSynchronize(s)); // (the scratch above is freed on return)
     return KNHIP_OK;
 }
@@ -179,10 +190,20 @@ int kmeans_impl(int device, int metric, int d, int64_t n, const float* d_x, int6
         HIP_TRY(inv_norm.alloc((size_t)k * sizeof(float)));
         HIP_TRY(launch_renorm_rows(d_cen, k, d, inv_norm.as<float>(), nullptr));
     }
-    // -- iterations.  (The reference leaves the loop when the objective repeats bit for bit, Clustering.cpp:362-377 with
-    // early_stop_threshold 0: that is the fixed point of this deterministic loop, where further iterations reproduce
-    // the same centroids -- running them changes nothing.)
-    DevBuf keys64, keys32, sorted_rows, seg_off, tmp, hassign_d;
+    // -- iterations.  The reference leaves the loop when the objective -- the assignment distances summed in row order in
+    // a float (Clustering.cpp:301-305) -- repeats bit for bit (Clustering.cpp:362-377, early_stop_threshold 0).  That is NOT
+    // only the fixed point of the loop: a few rows far away (or inner products near 1e7) make the sum so large that a
+    // change of the other rows' assignment is below its last bit, and the reference stops while centroids still move.  So
+    // the same sum is formed here, on the host, from the distances of every iteration.
+    // It stops where the reference stops only while every distance is the reference's dis[] bit for bit: true of
+    // nearest_small_kernel and of the coarse search's k = 1 distances, whose exact re-rank makes the prefilter routes (k >=
+    // 2048 centroids) return the all-pairs kernel's bits (tests/test_gpu_value_dists.py: test_coarse_stage).  The hostile-value
+    // k-means cases (tests/test_gpu_build_dists.py) reach the LDS kernel and the all-pairs kernel only: an early stop behind a
+    // prefilter route is not covered by a test.
+    DevBuf keys64, keys32, sorted_rows, seg_off, tmp, hassign_d, adis_d;
+    HIP_TRY(adis_d.alloc((size_t)nx * sizeof(float)));
+    std::vector<float> adis((size_t)nx);
+    float prev_obj = 0.f;
     HIP_TRY(sorted_rows.alloc((size_t)nx * sizeof(int32_t)));
     HIP_TRY(seg_off.alloc((size_t)(k + 1) * sizeof(int64_t)));
     const size_t tmp_bytes = group_rows_tmp_bytes(nx, k);
@@ -208,12 +229,12 @@ int kmeans_impl(int device, int metric, int d, int64_t n, const float* d_x, int6
     std::vector<float> hassign((size_t)k), cen_h;
     for (int it = 0; it < tp.niter; it++) {
         if (small) {
-            HIP_TRY(launch_nearest_small(xs, nx, d, 0, d, d_cen, (int)k, keys32.as<int32_t>(), nullptr));
+            HIP_TRY(launch_nearest_small(xs, nx, d, 0, d, d_cen, (int)k, keys32.as<int32_t>(), adis_d.as<float>(), nullptr));
             HIP_TRY(group_rows_by_key(nullptr, keys32.as<int32_t>(), nx, k, sorted_rows.as<int32_t>(),
                                       seg_off.as<int64_t>(), tmp.p, tmp_bytes, nullptr));
         } else {
             if (int rc = knhip_index_set_coarse_device(assigner, d_cen)) return rc;
-            if (int rc = assign_rows(assigner, xs, nx, keys64.as<int64_t>(), nullptr)) return rc;
+            if (int rc = assign_rows(assigner, xs, nx, keys64.as<int64_t>(), nullptr, adis_d.as<float>())) return rc;
             HIP_TRY(group_rows_by_key(keys64.as<int64_t>(), nullptr, nx, k, sorted_rows.as<int32_t>(),
                                       seg_off.as<int64_t>(), tmp.p, tmp_bytes, nullptr));
         }
@@ -233,6 +254,19 @@ int kmeans_impl(int device, int metric, int d, int64_t n, const float* d_x, int6
         if (tp.spherical) { // post_process_centroids after the update and the split (Clustering.cpp:347)
             HIP_TRY(launch_renorm_rows(d_cen, k, d, inv_norm.as<float>(), nullptr));
         }
+        HIP_TRY(hipMemcpy(adis.data(), adis_d.p, (size_t)nx * sizeof(float), hipMemcpyDeviceToHost));
+        float obj = 0.f;
+        for (int64_t i = 0; i < nx; i++) {
+            obj += adis[(size_t)i];
+        }
+        if (it > 0) { // (the centroids of THIS iteration are the result: the reference tests after its update)
+            const double change = prev_obj == 0 ? std::numeric_limits<double>::max()
+                                                : (double)(std::fabs(prev_obj - obj) / std::fabs(prev_obj));
+            if (change <= 0.0) {
+                break;
+            }
+        }
+        prev_obj = obj;
     }
     HIP_TRY(hipDeviceSynchronize());
     return KNHIP_OK;
@@ -320,6 +354,9 @@ int add_device_impl(knhip_index* idx, int64_t n, const float* d_x, const int64_t
     const int64_t nlist = idx->nlist;
     const int64_t cs = idx->dev_code_size();
     const int64_t n0 = idx->has_data ? idx->ntotal : 0;
+    // IndexIVF::add_core: the id of row i is ntotal + i and ntotal += n, whether or not rows were skipped (IndexIVF.cpp:263,
+    // 286) -- the reference's ntotal counts the rows OFFERED
+    const int64_t offered0 = idx->has_data ? idx->noffered : 0;
     DevBuf assign, codes, ids_new, sorted_rows, seg_off, tmp;
     HIP_TRY(assign.alloc((size_t)n * sizeof(int64_t)));
     if (idx->row_type != KNHIP_ROWTYPE_FP32) {
@@ -335,7 +372,7 @@ int add_device_impl(knhip_index* idx, int64_t n, const float* d_x, const int64_t
     const int64_t* new_ids = d_ids;
     if (!d_ids) { // Knowhere ids are the running row numbers (IvfIndexNode::Add -> add_core without xids)
         HIP_TRY(ids_new.alloc((size_t)n * sizeof(int64_t)));
-        HIP_TRY(launch_iota_i64(ids_new.as<int64_t>(), n, n0, nullptr));
+        HIP_TRY(launch_iota_i64(ids_new.as<int64_t>(), n, offered0, nullptr));
         new_ids = ids_new.as<int64_t>();
     }
     HIP_TRY(sorted_rows.alloc((size_t)n * sizeof(int32_t)));
@@ -359,8 +396,9 @@ int add_device_impl(knhip_index* idx, int64_t n, const float* d_x, const int64_t
     if (n0) {
         if (int rc = ensure_aos(idx)) return rc;
     }
-    HIP_TRY(out_codes.alloc((size_t)(n0 + n) * cs));
-    HIP_TRY(out_ids.alloc((size_t)(n0 + n) * sizeof(int64_t)));
+    const int64_t nout = off[(size_t)nlist]; // (n0 + the rows of the batch that have a centroid)
+    HIP_TRY(out_codes.alloc((size_t)nout * cs));
+    HIP_TRY(out_ids.alloc((size_t)nout * sizeof(int64_t)));
     HIP_TRY(launch_merge_lists(n0 ? idx->codes_aos.as<uint8_t>() : nullptr, n0 ? idx->ids.as<int64_t>() : nullptr,
                                n0 ? old_off.as<int64_t>() : nullptr, codes.as<uint8_t>(), new_ids,
                                sorted_rows.as<int32_t>(), seg_off.as<int64_t>(), out_off.as<int64_t>(), nlist, cs,
@@ -371,7 +409,9 @@ int add_device_impl(knhip_index* idx, int64_t n, const float* d_x, const int64_t
     std::swap(idx->codes_aos.bytes, out_codes.bytes);
     std::swap(idx->ids.p, out_ids.p);
     std::swap(idx->ids.bytes, out_ids.bytes);
-    return build_list_layout(idx, off, idx->codes_aos.as<uint8_t>(), idx->ids.as<int64_t>());
+    if (int rc = build_list_layout(idx, off, idx->codes_aos.as<uint8_t>(), idx->ids.as<int64_t>())) return rc;
+    idx->noffered = offered0 + n;
+    return KNHIP_OK;
 }
 
 int train_device_impl(knhip_index* idx, int64_t n, const float* d_x, const knhip_train_params* p) {

@@ -226,7 +226,10 @@ struct knhip_index {
     DevBuf sq_trained;    // vmin[d], vdiff[d]
     // lists / base
     bool has_data = false;
-    int64_t ntotal = 0;
+    int64_t ntotal = 0;   // rows STORED (IVF kinds: the sum of the list sizes)
+    int64_t noffered = 0; // IndexIVF::ntotal: rows OFFERED to Add, those without a centroid (skipped, not stored) included --
+                          // what knhip_index_count reports and where the default ids of the next Add start; equal to
+                          // ntotal wherever the lists are replaced (add_lists, set_lists_device, add_vectors)
     int64_t code_size = 0;
     int sq_bits = 8;      // IVF_SQ8: code width (sq_type SQ8 / SQ6 / SQ4); code_size = sq_code_size(d, sq_bits)
     int row_type = 0;     // IVF_FLAT: KNHIP_ROWTYPE_* of the resident rows (`rows`, `codes_aos`); code_size stays 4 d (the host's view)

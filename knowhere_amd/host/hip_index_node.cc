@@ -1134,10 +1134,12 @@ class HipIndexNode : public IndexNode {
             x.ids.assign(nlist_, {});
             std::vector<int64_t> all_sizes((size_t)nlist_, 0);
             for (const auto& s : sh_) {
-                const int64_t cnt = knhip_index_count(s.idx.p);
-                if (cnt == 0) continue;
+                if (knhip_index_count(s.idx.p) == 0) continue;
                 std::vector<int64_t> sizes((size_t)nlist_);
                 if ((rc = knhip_index_get_list_sizes(s.idx.p, sizes.data()))) return ToStatus(rc);
+                // (the rows STORED: knhip_index_count also counts the rows an Add skipped)
+                const int64_t cnt = std::accumulate(sizes.begin(), sizes.end(), (int64_t)0);
+                if (cnt == 0) continue;
                 std::vector<uint8_t> codes((size_t)cnt * CodeSize());
                 std::vector<int64_t> ids((size_t)cnt);
                 if ((rc = knhip_index_get_lists(s.idx.p, codes.data(), ids.data()))) return ToStatus(rc);
@@ -1303,7 +1305,9 @@ class HipIndexNode : public IndexNode {
                     return Status::invalid_serialized_index_type;
                 sum += (int64_t)n;
             }
-            if (sum != ntotal) return Status::invalid_serialized_index_type;
+            // IndexIVF::ntotal counts the rows OFFERED to Add: a row without a centroid (NaN, inf, an overflowing norm) is
+            // skipped yet counted (IndexIVF.cpp:286), so the lists may hold fewer rows than the header says -- never more
+            if (sum > ntotal) return Status::invalid_serialized_index_type;
             if (x.has_refine) {
                 if (x.refine_is_sq ? (x.refine_sq.hdr.ntotal != ntotal || x.refine_sq.hdr.d != d)
                                    : (x.refine_index.hdr.ntotal != ntotal || x.refine_index.hdr.d != d ||
@@ -1421,6 +1425,14 @@ class HipIndexNode : public IndexNode {
                 }
                 return bail(rc);
             }
+        }
+        {  // Count() is the blob's ntotal, skipped rows included; the surplus is booked on the first shard (CountLocked sums)
+            int64_t stored = 0, stored0 = 0;
+            for (int64_t l = 0; l < nlist_; l++) {
+                stored += sizes[l];
+                if (W == 1 || owner_[(size_t)l] == 0) stored0 += sizes[l];
+            }
+            if (ntotal > stored && (rc = knhip_index_set_count(sh_[0].idx.p, stored0 + (ntotal - stored)))) return bail(rc);
         }
         if (StoredNormCosine()) {
             const Status st = PushRowScale();
@@ -1929,8 +1941,14 @@ class HipIndexNode : public IndexNode {
     Status
     PushRowScale() {
         for (auto& s : sh_) {
-            const int64_t count = knhip_index_count(s.idx.p);
+            int64_t count = knhip_index_count(s.idx.p);
             if (count <= 0) continue;
+            if constexpr (Kind != KNHIP_BRUTE_FORCE) {  // (the rows STORED: count also holds the rows an Add skipped)
+                std::vector<int64_t> sizes((size_t)nlist_);
+                if (int rc = knhip_index_get_list_sizes(s.idx.p, sizes.data())) return ToStatus(rc);
+                count = std::accumulate(sizes.begin(), sizes.end(), (int64_t)0);
+                if (count <= 0) continue;
+            }
             std::vector<float> canon((size_t)count);
             if constexpr (Kind == KNHIP_BRUTE_FORCE) {
                 if (s.row_base < 0 || s.row_base + count > (int64_t)row_scale_by_id_.size()) return Status::invalid_args;

@@ -233,7 +233,12 @@ class GpuIndex:
     # ---- info ----
     @property
     def count(self):
+        """IndexIVF::ntotal: the rows offered to add(), those without a centroid (skipped) included"""
         return int(self.L.knhip_index_count(self.h))
+
+    def set_count(self, n):
+        """a loader's call after add_lists / set_lists_device: the ntotal of the index it read (>= the rows stored)"""
+        check(self.L.knhip_index_set_count(self.h, int(n)))
 
     @property
     def device_bytes(self):
